@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- RealNVP fit+sample throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 Workload (BASELINE.json configs[1], "C2"): n = 1M rows per GPU of make_moons-shaped tabular data, d=16,
 cond=4, 8 coupling layers, hidden=(128,).  One STEP = one pass of the hot path over the rank's data set:
@@ -16,16 +16,17 @@ the same Adam step; sampling shards the global N x 1M rows with no collective.
 
 Batch regimes with N > 1: by default every rank's share of a step stays 65 536 rows (--per-rank-batch; the global batch grows with N);
 --global-batch 65536 shares the reference's ONE batch_size (realnvp.py:237; SURVEY.md 8(d)/(e)'s headline) out over the ranks -- 8 192 rows
-per rank at 8 GPUs.  A default run with N > 1 also times the global-batch regime after the timed region
-(config.global_batch_65536_regime), and exits with code 3 (line still printed, with "error") if the library's RCCL communicator
-does not span all ranks or the replicas' parameters differ afterwards.
-Timing: exactly --steps steps between barrier + synchronize form a block; when a block is shorter than a second it is repeated up to
-about six seconds (the driver's GPU-busy sampler has a ~5 s period) and the MEDIAN block is reported (timed_blocks, block_seconds).
+per rank at 8 GPUs.  A --full run with N > 1 also times the global-batch regime after the timed region
+(config.global_batch_65536_regime).  A run with N > 1 exits with code 3 (line still printed, with "error") if the library's RCCL
+communicator does not span all ranks or the replicas' parameters differ afterwards.
+Timing: the timed region is exactly --steps steps, after --warmup untimed ones, between barrier + synchronize on both sides;
+ms_per_step = its time / --steps.  --dump-outputs DIR writes what the last timed step computed (dump_outputs).
 
 With --gpus N > 1 and no WORLD_SIZE in the environment this script starts its own N ranks (child processes
 of `python -m torch.distributed.run`; nothing in the parent touches the GPU) and relays their output.
 
-`value` = rows (fit rows + sampled rows) per second over all GPUs.  The JSON line also carries
+`value` = rows (fit rows + sampled rows) per second over all GPUs.  A plain run prints the headline line (metric, value, unit,
+higher_is_better, dtype, ms_per_step, steps, config, ...).  With --full the JSON line also carries
   roofline        -- the dominant kernel (fused forward+backward) against the f32 MFMA peak, from HIP events
                      around every one of its launches inside the timed region;
   roofline_kernels-- the same for the sampling kernel (timed region) and the log-prob kernel (measured after it);
@@ -108,6 +109,26 @@ def make_data(n, d, c, seed):
     lab = np.stack(labels, 1)
     C = lab[:, :c] if c <= lab.shape[1] else np.concatenate([lab, rng.normal(size=(n, c - lab.shape[1]))], 1)
     return X.astype(np.float32), C.astype(np.float32)
+
+
+DUMP_SAMPLE_BYTES = 16 << 20        # the sampled rows written by --dump-outputs: a fixed, seeded subset of at most this many bytes
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(out_dir, xs, losses, params):
+    """--dump-outputs: what the timed path handed its caller in the LAST timed step, as float32 .npy files --
+    samples.npy: rows of that step's sample() (a fixed, seeded subset of the rows, ascending, DUMP_SAMPLE_BYTES at most);
+    losses.npy: that fit epoch's per-batch losses (workloads that fit); params.npy: the flat parameters after it"""
+    os.makedirs(out_dir, exist_ok=True)
+    n, d = xs.shape
+    k = min(n, DUMP_SAMPLE_BYTES // (4 * d))
+    rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=k, replace=False))
+    import torch
+    idx = torch.from_numpy(rows).to(xs.device)
+    np.save(os.path.join(out_dir, "samples.npy"), xs.index_select(0, idx).cpu().numpy().astype(np.float32))
+    if losses is not None:
+        np.save(os.path.join(out_dir, "losses.npy"), losses.detach().cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "params.npy"), params.detach().reshape(-1).cpu().numpy().astype(np.float32))
 
 
 def train_mixed_bound_seconds_per_row(d, c, hidden, L):
@@ -636,6 +657,12 @@ def main():
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c2",
                     help="c2 (default: the configuration the metric is quoted on), c3 (fit + sample, d=32 cond=8 L=12 hidden 256, "
                          "1M rows per GPU) or c4 (sampling only, d=64 cond=16, 2M draws per GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure, after the timed steps: roofline and per-kernel figures, the other batch "
+                         "regime (N > 1), api_level, secondary_configs, the CPU baselines and the log-prob MAE against the oracle. "
+                         "Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32; see dump_outputs)")
     args = ap.parse_args()
     if args.global_batch is not None and args.per_rank_batch is not None:
         ap.error("--global-batch and --per-rank-batch exclude each other")
@@ -764,40 +791,26 @@ def main():
     for i in range(args.warmup):
         step(i)
     torch.cuda.synchronize()
-    # HIP events around the hot kernels, recorded by the library on the stream it launches on, for every
-    # launch of the timed region
-    MAX_BLOCKS = 512
-    TIMED_SECONDS = 6.0                                     # of GPU work between the first and the last clock reading (the driver's GPU-busy sampler has a ~5 s period)
-    _hip.profile_enable(args.steps * (nb + 1) + 8)          # one block's launches; read (and reset) after every block
-    prof = {"n_train": 0, "train_ms": 0.0, "n_inv": 0, "inv_ms": 0.0}
-
-    def timed_block():
-        """EXACTLY args.steps steps between barrier + synchronize on both sides; the MAX over the ranks"""
-        torch.cuda.synchronize()
-        if dp:
-            dist.barrier()
-        t0 = time.perf_counter()
-        for k in range(args.steps):
-            step(args.warmup + k)
-        torch.cuda.synchronize()
-        if dp:
-            dist.barrier()
-        t = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
-        if dp:
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        a, b = _hip.profile_read(_hip.PROFILE_TRAIN); prof["n_train"] += a; prof["train_ms"] += b      # outside the clock
-        a, b = _hip.profile_read(_hip.PROFILE_INVERSE); prof["n_inv"] += a; prof["inv_ms"] += b
-        return float(t.item())
-
-    # A block of --steps steps can be far shorter than the driver can see (20 steps of C2 = 0.11 s): the block is then repeated until
-    # about TIMED_SECONDS of GPU work have been timed and the MEDIAN block is reported (`steps` stays as passed, `timed_blocks` says
-    # how many).  Every rank derives the count from the same max-reduced first block.
-    block_s = [timed_block()]
-    n_blocks = max(1, min(MAX_BLOCKS, int(np.ceil(TIMED_SECONDS / max(block_s[0], 1e-6)))))
-    for _ in range(n_blocks - 1):
-        block_s.append(timed_block())
-    dt = float(np.median(block_s))
-    timed_steps = n_blocks * args.steps
+    # --full: HIP events around the hot kernels, recorded by the library on the stream it launches on, for every launch of the
+    # timed region (the roofline figures); a plain run records none
+    if args.full:
+        _hip.profile_enable(args.steps * (nb + 1) + 8)
+    # the timed region: EXACTLY --steps steps between barrier + synchronize on both sides; the MAX over the ranks
+    if dp:
+        dist.barrier()
+    t0 = time.perf_counter()
+    for k in range(args.steps):
+        step(args.warmup + k)
+    torch.cuda.synchronize()
+    if dp:
+        dist.barrier()
+    t = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
+    if dp:
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+    dt = float(t.item())
+    timed_steps = args.steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, xs, losses[n_steps - 1, :nb] if do_fit else None, eng.params)
 
     # N > 1 self-check, after the clock stopped: every rank applied the identical Adam update to the identical all-reduced
     # gradient, so the replicas must still hold the same bits -- a checksum of the flat parameter buffer (and the last batch
@@ -820,13 +833,15 @@ def main():
             dp_failure = "the library's RCCL communicator spans %d of %d ranks (fell back to the per-batch loop)" % (rccl_ranks, world)
         elif not replicas_identical:
             dp_failure = "the ranks' parameters / last loss differ after the timed region"
-    n_train, train_ms, n_inv, inv_ms = prof["n_train"], prof["train_ms"], prof["n_inv"], prof["inv_ms"]
+    if args.full:
+        n_train, train_ms = _hip.profile_read(_hip.PROFILE_TRAIN)          # the timed region's launches, read outside the clock
+        n_inv, inv_ms = _hip.profile_read(_hip.PROFILE_INVERSE)
     disp_last_timed = _hip.last_dispatch(_hip.PROFILE_TRAIN) if do_fit else None     # (read before the secondary regime below launches anything)
     # N > 1, default regime: the OTHER regime -- the reference's one global batch_size of 65 536 shared out over the ranks (SURVEY.md
     # 8(d)/(e)) -- is timed as well, after the clock stopped and outside `value`: a few fit epochs of N x 16 steps on the same
-    # resident rows, so that one scaling run yields both curves
+    # resident rows, so that one scaling run yields both curves (--full)
     other_regime = None
-    if world > 1 and do_fit and batch_mode == "per_rank":
+    if args.full and world > 1 and do_fit and batch_mode == "per_rank":
         g2 = BATCH
         gb2 = _engine.batch_bounds(N_ROWS * world, g2)
         sh2 = [_engine.shard_bounds(s, e, rank, world) for (s, e) in gb2]
@@ -864,11 +879,16 @@ def main():
         full = _hip.last_dispatch(_hip.PROFILE_TRAIN)
         full["launches"] = disp_train["launches"]; full["ragged_batch"] = {k: disp_train[k] for k in ("kernel", "variant", "row_tiles", "grid", "rows")}
         disp_train = full
-    assert n_train == timed_steps * nb and n_inv == timed_steps * (1 if do_sample else 0), (n_train, n_inv, timed_steps)
+    if args.full:
+        assert n_train == timed_steps * nb and n_inv == timed_steps * (1 if do_sample else 0), (n_train, n_inv, timed_steps)
     final_loss = float(losses[n_steps - 1, nb - 1].item()) if do_fit else None
     assert final_loss is None or np.isfinite(final_loss), "training diverged"
 
-    if rank == 0:
+    if rank == 0 and not args.full:
+        eng.forward(X, C, want_z=False, want_logp=True)       # one untimed log-prob call: its dispatch record is what `dtype` names
+        torch.cuda.synchronize()
+        disp_fwd = _hip.last_dispatch(_hip.PROFILE_FORWARD)
+    if rank == 0 and args.full:
         # log-prob kernel (not part of fit+sample): measured here, after the timed region
         for _ in range(20):         # (tens of ms of warm-up: the dispatch queries above let the chip's clock fall)
             eng.forward(X, C, want_z=False, want_logp=True)
@@ -883,61 +903,10 @@ def main():
 
     if rank == 0:
         rows_per_step = (int(do_fit) + int(do_sample)) * N_ROWS * world
-        f1 = useful_flops_per_row(D, CDIM, HIDDEN, LAYERS, 1)
-        train_tf = 3 * f1 * N_ROWS * timed_steps / (train_ms * 1e-3) / 1e12 if do_fit else None     # fwd + dgrad + wgrad
-        inv_tf = f1 * N_ROWS * timed_steps / (inv_ms * 1e-3) / 1e12
-        fwd_tf = f1 * N_ROWS * n_fwd / (fwd_ms * 1e-3) / 1e12
         path = _hip.kernel_path(eng.shape, eng.masks_host, _hip.OP_TRAIN)
-        kname = disp_train["kernel"] if do_fit else None
         train_bx3 = do_fit and disp_train["gemm1_fwd"] == "bx3"
         flow_bx3 = (disp_inv or disp_fwd)["gemm1_fwd"] == "bx3"
-        flow_kernel = (disp_inv or disp_fwd)["kernel"]
         fwd_bx3, fwd_kernel = disp_fwd["gemm1_fwd"] == "bx3", disp_fwd["kernel"]
-        mixed = mixed_bound_seconds_per_row(D, CDIM, HIDDEN, LAYERS)
-        last_share = shares[-1][1] - shares[-1][0]
-        batches_text = ("%d of every %d on %d rows, 1 on %d" % (nb - 1, nb, rank_batch, last_share) if last_share != rank_batch
-                        else "every launch on %d rows" % rank_batch)
-        if do_fit:
-            roof = {"bound": "mfma", "achieved": train_tf, "peak": F32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                    "frac": train_tf / F32_MFMA_PEAK_TFLOPS,
-                    "frac_mixed_bound": (train_mixed_bound_seconds_per_row(D, CDIM, HIDDEN, LAYERS) * N_ROWS * timed_steps / (train_ms * 1e-3)
-                                         if train_bx3 else None),
-                    "traffic": pmc_traffic(kernel_prefix(disp_train, D, CDIM), TRAFFIC_FILE if args.workload == "c2" else TRAFFIC_FILE_C3C4),
-                    "dispatch": disp_train,
-                    "kernel": "%s (fused forward+backward; variant %s, %d row tiles per wave, %d waves per workgroup; GEMM1 of the "
-                              "forward phase on %s, everything else on f32 MFMA): %d launches in the timed region, %.3f ms avg (%s), "
-                              "%d useful flop/row x %d rows per epoch; %d kernel launches per "
-                              "batch; `frac` prices the useful flops against the f32 MFMA peak%s"
-                              % (kname, disp_train["variant"], disp_train["row_tiles"], disp_train["waves"],
-                                 "3-term split-bf16 MFMA (float32-level accuracy)" if train_bx3 else "f32 MFMA", n_train,
-                                 train_ms / n_train, batches_text, 3 * f1, N_ROWS, disp_train["launches"],
-                                 ", `frac_mixed_bound` against the bound of what runs (forward GEMM1 as six bf16 products per f32 "
-                                 "product on the dense bf16 peak)" if train_bx3 else "")}
-        else:           # sampling only (C4): the inverse kernel is the dominant one
-            roof = {"bound": "mfma", "achieved": inv_tf, "peak": F32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                    "frac": inv_tf / F32_MFMA_PEAK_TFLOPS,
-                    # the committed PMC profile has this kernel at 1M rows per launch; scaled to this launch's rows
-                    "traffic": (lambda t: None if t is None else t * N_ROWS / 1048576.0)(pmc_traffic(kernel_prefix(disp_inv, D, CDIM, True), TRAFFIC_FILE_C3C4)),
-                    "frac_mixed_bound": mixed * N_ROWS * timed_steps / (inv_ms * 1e-3) if flow_bx3 else None,
-                    "kernel": "%s inverse with the prior drawn in-kernel: %d launches of %d rows in the timed region, %.3f ms avg, "
-                              "%d useful flop/row; `frac` prices it against the f32 MFMA peak, `frac_mixed_bound` against the "
-                              "bound of what it executes (GEMM1 as six bf16 products per f32 product on the bf16 peak, "
-                              "GEMM2 on f32 MFMA)" % (flow_kernel, n_inv, N_ROWS, inv_ms / n_inv, f1)}
-        sample_entry = {"bound": "mfma", "achieved": inv_tf, "peak": F32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                        "frac": inv_tf / F32_MFMA_PEAK_TFLOPS, "ms_per_launch": inv_ms / max(n_inv, 1),
-                        "rows_per_launch": N_ROWS, "launches": n_inv, "where": "timed region"}
-        fwd_entry = {"bound": "mfma", "achieved": fwd_tf, "peak": F32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                     "frac": fwd_tf / F32_MFMA_PEAK_TFLOPS, "ms_per_launch": fwd_ms / n_fwd, "rows_per_launch": N_ROWS,
-                     "launches": n_fwd, "where": "after the timed region"}
-        sample_entry["dispatch"], fwd_entry["dispatch"] = disp_inv, disp_fwd
-        if do_sample:       # HBM bytes per launch of the sampling kernel from the committed PMC profile (None when the sources moved)
-            t = pmc_traffic(kernel_prefix(disp_inv, D, CDIM, True), TRAFFIC_FILE if args.workload == "c2" else TRAFFIC_FILE_C3C4)
-            sample_entry["traffic"] = None if t is None else t * N_ROWS / 1048576.0
-            sample_entry["algorithmic_bytes"] = 4 * N_ROWS * (CDIM + D)     # conditions in, samples out: the prior is drawn in the kernel
-        if flow_bx3 and do_sample:
-            sample_entry["frac_mixed_bound"] = mixed * N_ROWS * timed_steps / (inv_ms * 1e-3)
-        if fwd_bx3:
-            fwd_entry["frac_mixed_bound"] = mixed * N_ROWS * n_fwd / (fwd_ms * 1e-3)
         gemm1_text = "3-term split-bf16 MFMA, float32-level accuracy"
         dtype = "f32"
         if train_bx3 or flow_bx3:
@@ -954,8 +923,7 @@ def main():
         out = {
             "metric": "RealNVP samples/sec (fit+sample)", "value": rows_per_step * args.steps / dt,
             "unit": "rows/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3, "timed_blocks": n_blocks,
-            "block_seconds": {"median": dt, "min": float(min(block_s)), "max": float(max(block_s))},
+            "ms_per_step": dt / args.steps * 1e3, "timed_blocks": 1,
             "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": dtype, "data": "synthetic",
             "config": {"workload": "%s: RealNVP n=%d/GPU d=%d cond=%d L=%d hidden=%r; one step = %s"
@@ -966,59 +934,111 @@ def main():
                        "parallelism": "dp%d" % world, "global_batch_65536_regime": other_regime,
                        "rccl_ranks": rccl_ranks, "replicas_identical": replicas_identical,
                        "kernel_path": "mfma" if path == _hip.PATH_MFMA else "generic", "final_loss": final_loss},
-            "roofline": roof,
-            "roofline_kernels": {
-                "sample (%s inverse, prior drawn in-kernel)" % flow_kernel: sample_entry,
-                "log_prob (%s forward)" % fwd_kernel: fwd_entry},
-            "device_resident": {"fit_rows_per_s": None, "sample_rows_per_s": N_ROWS * world / (inv_ms / timed_steps * 1e-3),
-                                "note": "sample: kernel time only; fit: ms_per_step minus the sampling kernels' time"},
         }
-        if do_fit:
-            out["device_resident"]["fit_rows_per_s"] = N_ROWS * world / max(dt / args.steps - inv_ms / timed_steps * 1e-3, 1e-9)
-        if do_sample and not args.no_api_level:
-            _hip.profile_enable(64)
-            ref_stream = reference_stream_sampling(eng, C, dev)
-            _hip.profile_enable(0)
-            if ref_stream is not None:
-                out["roofline_kernels"]["sample with the reference's prior stream (mt19937 + Box-Muller on the device, then %s inverse)" % flow_kernel] = ref_stream
-        params = eng.params.detach().cpu().numpy()
-        if world == 1 and not force_dist and not args.no_api_level and args.workload == "c2":
-            out["api_level"] = api_level(Xh, Ch, dev)
-            out["secondary_configs"] = secondary_configs(Xh, Ch, dev)
-        if not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(Xh, Ch)
-            if args.workload == "c2":
-                out["cpu_baseline_c_oracle"] = cpu_baseline_oracle(Xh, Ch, params)
-        # second half of BASELINE.json's metric (every workload, whatever else is switched off): per-row log-prob MAE of
-        # the HIP path against the CPU restatement of the reference (float32 oracle, and its float64 referee) on the
-        # weights the run ends with (trained where the workload fits, the random init for c4), 4096 rows
-        from oracle import Oracle, Shape
-        rows = 4096
-        lp = nf.log_prob_samples(X[:rows], C[:rows]).detach().cpu().numpy()
-        sh = Shape.make(LAYERS, D, CDIM, HIDDEN, "tanh")
-        _, lp32, _ = Oracle(32).log_prob(sh, params, Xh[:rows], Ch[:rows])
-        _, lp64, _ = Oracle(64).log_prob(sh, params, Xh[:rows], Ch[:rows])
-        out["logprob_mae"] = {"vs_oracle_f32": float(np.abs(lp - lp32).mean()),
-                              "vs_oracle_f64": float(np.abs(lp - lp64).mean()),
-                              "oracle_f32_vs_f64": float(np.abs(lp32 - lp64).mean()), "rows": rows,
-                              "mean_abs_logp": float(np.abs(lp64).mean()),
-                              # north_star: 1e-5.  For the d >= 32 shapes |log p| runs to several hundred, one float32 ulp there is
-                              # 3e-5 ... 6e-5, and the float32 oracle ITSELF sits 1.2e-5 from its float64 referee (oracle_f32_vs_f64):
-                              # the tests' bar for those shapes is 3e-5 AND no further from float64 than 3x the reference's own distance
-                              "target": 1e-5 if args.workload == "c2" else 3e-5}
         # the two batch regimes, where nobody can miss them: `value` is measured in `batch_regime`; the other one is reported beside
         # it (N > 1: timed after the clock stopped; N = 1: what ONE rank of an 8-GPU job executes per step, secondary_configs)
         out["batch_regime"] = ("weak batch: %d rows per rank and step, the global batch grows with N" % rank_batch if batch_mode == "per_rank"
                                else "strong batch: the reference's ONE global batch of %d rows shared out over the %d ranks" % (gbatch, world)) if do_fit else None
-        if other_regime is not None:
-            out["strong_batch_regime_global_65536"] = other_regime
-        d8 = out.get("secondary_configs", {}).get("dp8_rank_steps")
-        if d8:
-            out["strong_batch_8gpu_projection"] = {
-                "eight_rank_steps_over_one_gpu_step": {k: v["eight_rank_steps_over_one_gpu_step"] for k, v in d8.items() if isinstance(v, dict) and "eight_rank_steps_over_one_gpu_step" in v},
-                "note": "global batch 65536 over 8 ranks = 8192 rows per rank: 8 x (rows/s of one rank's step, measured on this GPU through "
-                        "rnvp_fit_epoch_dp on a one-rank RCCL communicator) / (rows/s of the one-GPU 65536-row step); the cross-GPU all-reduce "
-                        "latency comes on top -- north_star's >= 6x is NOT projected in this regime, the weak-batch regime keeps the one-GPU step"}
+        if args.full:
+            f1 = useful_flops_per_row(D, CDIM, HIDDEN, LAYERS, 1)
+            train_tf = 3 * f1 * N_ROWS * timed_steps / (train_ms * 1e-3) / 1e12 if do_fit else None     # fwd + dgrad + wgrad
+            inv_tf = f1 * N_ROWS * timed_steps / (inv_ms * 1e-3) / 1e12
+            fwd_tf = f1 * N_ROWS * n_fwd / (fwd_ms * 1e-3) / 1e12
+            kname = disp_train["kernel"] if do_fit else None
+            flow_kernel = (disp_inv or disp_fwd)["kernel"]
+            mixed = mixed_bound_seconds_per_row(D, CDIM, HIDDEN, LAYERS)
+            last_share = shares[-1][1] - shares[-1][0]
+            batches_text = ("%d of every %d on %d rows, 1 on %d" % (nb - 1, nb, rank_batch, last_share) if last_share != rank_batch
+                            else "every launch on %d rows" % rank_batch)
+            if do_fit:
+                roof = {"bound": "mfma", "achieved": train_tf, "peak": F32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                        "frac": train_tf / F32_MFMA_PEAK_TFLOPS,
+                        "frac_mixed_bound": (train_mixed_bound_seconds_per_row(D, CDIM, HIDDEN, LAYERS) * N_ROWS * timed_steps / (train_ms * 1e-3)
+                                             if train_bx3 else None),
+                        "traffic": pmc_traffic(kernel_prefix(disp_train, D, CDIM), TRAFFIC_FILE if args.workload == "c2" else TRAFFIC_FILE_C3C4),
+                        "dispatch": disp_train,
+                        "kernel": "%s (fused forward+backward; variant %s, %d row tiles per wave, %d waves per workgroup; GEMM1 of the "
+                                  "forward phase on %s, everything else on f32 MFMA): %d launches in the timed region, %.3f ms avg (%s), "
+                                  "%d useful flop/row x %d rows per epoch; %d kernel launches per "
+                                  "batch; `frac` prices the useful flops against the f32 MFMA peak%s"
+                                  % (kname, disp_train["variant"], disp_train["row_tiles"], disp_train["waves"],
+                                     "3-term split-bf16 MFMA (float32-level accuracy)" if train_bx3 else "f32 MFMA", n_train,
+                                     train_ms / n_train, batches_text, 3 * f1, N_ROWS, disp_train["launches"],
+                                     ", `frac_mixed_bound` against the bound of what runs (forward GEMM1 as six bf16 products per f32 "
+                                     "product on the dense bf16 peak)" if train_bx3 else "")}
+            else:           # sampling only (C4): the inverse kernel is the dominant one
+                roof = {"bound": "mfma", "achieved": inv_tf, "peak": F32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                        "frac": inv_tf / F32_MFMA_PEAK_TFLOPS,
+                        # the committed PMC profile has this kernel at 1M rows per launch; scaled to this launch's rows
+                        "traffic": (lambda t: None if t is None else t * N_ROWS / 1048576.0)(pmc_traffic(kernel_prefix(disp_inv, D, CDIM, True), TRAFFIC_FILE_C3C4)),
+                        "frac_mixed_bound": mixed * N_ROWS * timed_steps / (inv_ms * 1e-3) if flow_bx3 else None,
+                        "kernel": "%s inverse with the prior drawn in-kernel: %d launches of %d rows in the timed region, %.3f ms avg, "
+                                  "%d useful flop/row; `frac` prices it against the f32 MFMA peak, `frac_mixed_bound` against the "
+                                  "bound of what it executes (GEMM1 as six bf16 products per f32 product on the bf16 peak, "
+                                  "GEMM2 on f32 MFMA)" % (flow_kernel, n_inv, N_ROWS, inv_ms / n_inv, f1)}
+            sample_entry = {"bound": "mfma", "achieved": inv_tf, "peak": F32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                            "frac": inv_tf / F32_MFMA_PEAK_TFLOPS, "ms_per_launch": inv_ms / max(n_inv, 1),
+                            "rows_per_launch": N_ROWS, "launches": n_inv, "where": "timed region"}
+            fwd_entry = {"bound": "mfma", "achieved": fwd_tf, "peak": F32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                         "frac": fwd_tf / F32_MFMA_PEAK_TFLOPS, "ms_per_launch": fwd_ms / n_fwd, "rows_per_launch": N_ROWS,
+                         "launches": n_fwd, "where": "after the timed region"}
+            sample_entry["dispatch"], fwd_entry["dispatch"] = disp_inv, disp_fwd
+            if do_sample:       # HBM bytes per launch of the sampling kernel from the committed PMC profile (None when the sources moved)
+                t = pmc_traffic(kernel_prefix(disp_inv, D, CDIM, True), TRAFFIC_FILE if args.workload == "c2" else TRAFFIC_FILE_C3C4)
+                sample_entry["traffic"] = None if t is None else t * N_ROWS / 1048576.0
+                sample_entry["algorithmic_bytes"] = 4 * N_ROWS * (CDIM + D)     # conditions in, samples out: the prior is drawn in the kernel
+            if flow_bx3 and do_sample:
+                sample_entry["frac_mixed_bound"] = mixed * N_ROWS * timed_steps / (inv_ms * 1e-3)
+            if fwd_bx3:
+                fwd_entry["frac_mixed_bound"] = mixed * N_ROWS * n_fwd / (fwd_ms * 1e-3)
+            out["roofline"] = roof
+            out["roofline_kernels"] = {
+                "sample (%s inverse, prior drawn in-kernel)" % flow_kernel: sample_entry,
+                "log_prob (%s forward)" % fwd_kernel: fwd_entry}
+            out["device_resident"] = {"fit_rows_per_s": None, "sample_rows_per_s": N_ROWS * world / (inv_ms / timed_steps * 1e-3),
+                                      "note": "sample: kernel time only; fit: ms_per_step minus the sampling kernels' time"}
+            if do_fit:
+                out["device_resident"]["fit_rows_per_s"] = N_ROWS * world / max(dt / args.steps - inv_ms / timed_steps * 1e-3, 1e-9)
+            if do_sample and not args.no_api_level:
+                _hip.profile_enable(64)
+                ref_stream = reference_stream_sampling(eng, C, dev)
+                _hip.profile_enable(0)
+                if ref_stream is not None:
+                    out["roofline_kernels"]["sample with the reference's prior stream (mt19937 + Box-Muller on the device, then %s inverse)" % flow_kernel] = ref_stream
+            params = eng.params.detach().cpu().numpy()
+            if world == 1 and not force_dist and not args.no_api_level and args.workload == "c2":
+                out["api_level"] = api_level(Xh, Ch, dev)
+                out["secondary_configs"] = secondary_configs(Xh, Ch, dev)
+            if not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(Xh, Ch)
+                if args.workload == "c2":
+                    out["cpu_baseline_c_oracle"] = cpu_baseline_oracle(Xh, Ch, params)
+            # second half of BASELINE.json's metric (--full, every workload, whatever else is switched off): per-row log-prob MAE of
+            # the HIP path against the CPU restatement of the reference (float32 oracle, and its float64 referee) on the
+            # weights the run ends with (trained where the workload fits, the random init for c4), 4096 rows
+            from oracle import Oracle, Shape
+            rows = 4096
+            lp = nf.log_prob_samples(X[:rows], C[:rows]).detach().cpu().numpy()
+            sh = Shape.make(LAYERS, D, CDIM, HIDDEN, "tanh")
+            _, lp32, _ = Oracle(32).log_prob(sh, params, Xh[:rows], Ch[:rows])
+            _, lp64, _ = Oracle(64).log_prob(sh, params, Xh[:rows], Ch[:rows])
+            out["logprob_mae"] = {"vs_oracle_f32": float(np.abs(lp - lp32).mean()),
+                                  "vs_oracle_f64": float(np.abs(lp - lp64).mean()),
+                                  "oracle_f32_vs_f64": float(np.abs(lp32 - lp64).mean()), "rows": rows,
+                                  "mean_abs_logp": float(np.abs(lp64).mean()),
+                                  # north_star: 1e-5.  For the d >= 32 shapes |log p| runs to several hundred, one float32 ulp there is
+                                  # 3e-5 ... 6e-5, and the float32 oracle ITSELF sits 1.2e-5 from its float64 referee (oracle_f32_vs_f64):
+                                  # the tests' bar for those shapes is 3e-5 AND no further from float64 than 3x the reference's own distance
+                                  "target": 1e-5 if args.workload == "c2" else 3e-5}
+            if other_regime is not None:
+                out["strong_batch_regime_global_65536"] = other_regime
+            d8 = out.get("secondary_configs", {}).get("dp8_rank_steps")
+            if d8:
+                out["strong_batch_8gpu_projection"] = {
+                    "eight_rank_steps_over_one_gpu_step": {k: v["eight_rank_steps_over_one_gpu_step"] for k, v in d8.items() if isinstance(v, dict) and "eight_rank_steps_over_one_gpu_step" in v},
+                    "note": "global batch 65536 over 8 ranks = 8192 rows per rank: 8 x (rows/s of one rank's step, measured on this GPU through "
+                            "rnvp_fit_epoch_dp on a one-rank RCCL communicator) / (rows/s of the one-GPU 65536-row step); the cross-GPU all-reduce "
+                            "latency comes on top -- north_star's >= 6x is NOT projected in this regime, the weak-batch regime keeps the one-GPU step"}
         if dp_failure:
             out["error"] = dp_failure
         os.write(json_fd, (json.dumps(out) + "\n").encode())

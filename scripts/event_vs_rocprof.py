@@ -16,7 +16,7 @@ calls = sum(int(r["Calls"]) for r in rows); tot = sum(float(r["TotalDurationNs"]
 n_ev = line["steps"] * 16
 # the timed region's launches are the LAST n_ev of the run (warm-up and the secondary legs come before / after): the CSV average
 # covers all of them, so also average the trace over the launches between the first and the last timed one when it is there
-res = {"command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline --no-api-level (one run: the JSON line's HIP events and the CSV describe the same launches)",
+res = {"command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline --no-api-level (one run: the JSON line's HIP events and the CSV describe the same launches)",
        "kernel": kern,
        # bench.py: achieved TFLOP/s = 245760 flop/row x 1e6 rows x steps / (sum of the event durations): inverted here
        "events_avg_ms_under_profiler": 245760 * 1e6 * line["steps"] / (line["roofline"]["achieved"] * 1e12) * 1e3 / n_ev,

@@ -3,7 +3,8 @@ set -x
 TAG=${1:-r1}
 cd /root/repo
 mkdir -p gpurun_out
-python bench.py --steps 32 --warmup 4 > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err
+OUT=$PWD/$_                  # the results folder made on the line above
+python bench.py --steps 32 --warmup 4 --full > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
 tail -3 gpurun_out/bench_$TAG.err
 cat gpurun_out/bench_$TAG.json
 export TMPDIR=/tmp

@@ -5,9 +5,10 @@
 # were copied into profiles/.
 TAG=${1:-r06}
 cd /root/repo; mkdir -p gpurun_out
+OUT=$PWD/$_                  # the results folder made on the line above
 python -m pytest tests -m gpu -x -q 2>&1 | grep -E "passed|failed|rror" | tail -5 > gpurun_out/${TAG}_gpu_tests.txt; cat gpurun_out/${TAG}_gpu_tests.txt
 bash scripts/gpu_micro.sh $TAG > gpurun_out/${TAG}_micro.log 2>&1 || echo "gpu_micro.sh FAILED (see gpurun_out/${TAG}_micro.log)"; tail -3 gpurun_out/${TAG}_micro_overlap.txt
-python bench.py --no-cpu-baseline --no-api-level > gpurun_out/${TAG}_bench_plain.json 2> gpurun_out/${TAG}_bench_plain.err
+python bench.py --full --no-cpu-baseline --no-api-level > $OUT/${TAG}_bench_plain.json 2> $OUT/${TAG}_bench_plain.err
 bash scripts/gpu_profiles.sh $TAG > gpurun_out/${TAG}_profiles.log 2>&1; tail -25 gpurun_out/${TAG}_profiles.log
 NT=65536 N=1048576 bash scripts/gpu_pmc.sh ${TAG}train c2 train > gpurun_out/${TAG}_train_pmc.log 2>&1
 python scripts/make_train_pmc.py $TAG
@@ -21,12 +22,12 @@ python scripts/make_train_pmc.py $TAG ${TAG}flowc2 "k_flow_bx3<2, 1" ${TAG}_flow
 N=1048576 bash scripts/gpu_pmc.sh ${TAG}flowc4 c4 fwd,inv > gpurun_out/${TAG}_flow_pmc_c4.log 2>&1
 python scripts/make_train_pmc.py $TAG ${TAG}flowc4 "k_flow_bx3<8, 4" ${TAG}_flow_pmc_c4.json "C4 forward / inverse, 1M rows, bx3 kernels (LDS-staged weights)"
 # single-rank data-parallel A/B: the same bench step through rnvp_fit_epoch (fused) and through rnvp_fit_epoch_dp on a one-rank RCCL communicator
-python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-api-level > gpurun_out/${TAG}_dp_a.json 2>/dev/null
-BENCH_FORCE_DIST=1 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-api-level > gpurun_out/${TAG}_dp_b.json 2>/dev/null
+python bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --no-api-level > $OUT/${TAG}_dp_a.json 2>/dev/null
+BENCH_FORCE_DIST=1 python bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --no-api-level > $OUT/${TAG}_dp_b.json 2>/dev/null
 python - <<PY
 import json
 a = json.load(open("gpurun_out/${TAG}_dp_a.json")); b = json.load(open("gpurun_out/${TAG}_dp_b.json"))
-out = {"command": "python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-api-level, without and with BENCH_FORCE_DIST=1 (one rank, RCCL initialised: rnvp_fit_epoch_dp = loss+grad, ncclAllReduce on the same stream, Adam per batch)",
+out = {"command": "python bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --no-api-level, without and with BENCH_FORCE_DIST=1 (one rank, RCCL initialised: rnvp_fit_epoch_dp = loss+grad, ncclAllReduce on the same stream, Adam per batch)",
        "fused_single_gpu_ms_per_step": a["ms_per_step"], "data_parallel_one_rank_ms_per_step": b["ms_per_step"],
        "ratio": b["ms_per_step"] / a["ms_per_step"], "fused_roofline_frac": a["roofline"]["frac"], "dp_roofline_frac": b["roofline"]["frac"]}
 json.dump(out, open("gpurun_out/${TAG}_dp_single_rank.json", "w"), indent=1); print(out)

@@ -7,6 +7,7 @@
 # The program itself follows `--` (python3 ...): no shell or env hop under the profiler.
 TAG=${1:-r06}
 cd /root/repo; mkdir -p gpurun_out; OUT=/root/repo/gpurun_out
+REPO=$PWD
 export TMPDIR=/tmp
 cd /tmp
 stats() {  # name, then the command
@@ -17,14 +18,14 @@ stats() {  # name, then the command
 }
 # the driver's own command (default steps / warmup), minus the CPU legs that launch no kernel; its JSON line (HIP events taken UNDER
 # the profiler) lands in ${TAG}_prof_bench.log and is compared with the CSV by scripts/event_vs_rocprof.py
-stats bench python3 /root/repo/bench.py --no-cpu-baseline --no-api-level
+stats bench python3 $REPO/bench.py --full --no-cpu-baseline --no-api-level
 export N=1048576 NT=65536
 stats kernels_c2 python3 /root/repo/scripts/bench_kernels.py c2
 stats kernels_c3 python3 /root/repo/scripts/bench_kernels.py c3
 stats kernels_c4 python3 /root/repo/scripts/bench_kernels.py c4
 EPOCHS=5 stats readme_c1 python3 /root/repo/scripts/readme_example.py
 for CNT in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --pmc $CNT --output-format csv -d $OUT/${TAG}_traffic/bench_$CNT -o p -- python3 /root/repo/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-api-level > $OUT/${TAG}_traffic.bench_$CNT.log 2>&1
+  rocprofv3 --pmc $CNT --output-format csv -d $OUT/${TAG}_traffic/bench_$CNT -o p -- python3 $REPO/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-api-level > $OUT/${TAG}_traffic.bench_$CNT.log 2>&1
   rocprofv3 --pmc $CNT --output-format csv -d $OUT/${TAG}_traffic/kern_$CNT -o p -- python3 /root/repo/scripts/bench_kernels.py c3 c4 > $OUT/${TAG}_traffic.kern_$CNT.log 2>&1
 done
 cd /root/repo

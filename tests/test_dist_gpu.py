@@ -87,7 +87,7 @@ def test_bench_self_launches_two_ranks_and_prints_one_json_line():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["BENCH_ONE_GPU"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=800)
+                        "--full", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -107,7 +107,7 @@ def test_bench_global_batch_mode_shares_one_batch_size_out_over_the_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["BENCH_ONE_GPU"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
-                        "--global-batch", "65536", "--no-cpu-baseline", "--no-api-level"], cwd=ROOT, env=env, capture_output=True,
+                        "--global-batch", "65536", "--full", "--no-cpu-baseline", "--no-api-level"], cwd=ROOT, env=env, capture_output=True,
                        text=True, timeout=800)
     assert r.returncode == 0, r.stderr[-3000:]
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
@@ -130,7 +130,7 @@ def test_bench_data_parallel_step_over_rccl_single_rank():
     """the N-rank step of bench.py with the real collective library: one rank, RCCL initialised, gradient
     all-reduce on RCCL's stream under the sampling kernel (BENCH_FORCE_DIST=1)"""
     env = dict(os.environ, BENCH_FORCE_DIST="1", MASTER_PORT=str(_free_port()))
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
