@@ -1,0 +1,108 @@
+"""ctypes binding of libpf_metrics.so (C ABI: probaforms_amd/metrics/csrc/pf_metrics.h).
+
+The library is built in-tree by `make -C probaforms_amd/metrics/csrc` (see __graft_entry__.build) and
+loaded on the first call, so importing probaforms_amd.metrics needs no GPU.  There is NO fallback: a
+missing library or a tensor off the HIP device raises.
+"""
+import ctypes as C
+import os
+import threading
+
+import torch
+
+ABI_VERSION = 100          # pfm_version() of the library this binding matches (pf_metrics.h PFM_VERSION)
+MOMENTS_MAX_D = 4096       # PFM_MOMENTS_MAX_D
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "csrc", "libpf_metrics.so")
+
+_VP, _I64, _SZ = C.c_void_p, C.c_int64, C.c_size_t
+
+_SIGNATURES = {
+    "pfm_version": (C.c_int, []),
+    "pfm_status_string": (C.c_char_p, [C.c_int]),
+    "pfm_mmd_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64]),
+    "pfm_mmd": (C.c_int, [_VP, _VP, _I64, _VP, _I64, _I64, _VP, _VP, _I64, _VP, _VP, _VP, _SZ]),
+    "pfm_moments_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64]),
+    "pfm_boot_moments": (C.c_int, [_VP, _VP, _I64, _VP, _I64, _I64, _VP, _VP, _I64, _VP, _VP, _VP, _SZ]),
+}
+EXPORTS = tuple(_SIGNATURES)
+
+_lib = None
+_lock = threading.Lock()
+
+
+class MetricsLibraryMissing(RuntimeError):
+    pass
+
+
+def lib():
+    """Load libpf_metrics.so once; raise loudly if it has not been built or is another ABI version."""
+    global _lib
+    if _lib is None:
+        with _lock:
+            if _lib is None:
+                if not os.path.exists(LIB_PATH):
+                    raise MetricsLibraryMissing(
+                        "%s not found: build it with `make -C probaforms_amd/metrics/csrc` "
+                        "(or `python -c 'import __graft_entry__ as g; g.build()'`). "
+                        "probaforms_amd.metrics has no CPU fallback." % LIB_PATH)
+                L = C.CDLL(LIB_PATH)
+                L.pfm_version.restype, L.pfm_version.argtypes = C.c_int, []
+                have = int(L.pfm_version())
+                if have != ABI_VERSION:
+                    raise MetricsLibraryMissing("%s reports pfm_version() = %d, this binding is written for %d: rebuild it "
+                                                "(`make -C probaforms_amd/metrics/csrc`)" % (LIB_PATH, have, ABI_VERSION))
+                for name, (res, args) in _SIGNATURES.items():
+                    fn = getattr(L, name)
+                    fn.restype, fn.argtypes = res, args
+                _lib = L
+    return _lib
+
+
+def check(status, what):
+    if status != 0:
+        msg = lib().pfm_status_string(status)
+        raise RuntimeError("%s failed: %s (status %d)" % (what, msg.decode() if msg else "?", status))
+
+
+def _ptr(t, dtype, what):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError("%s must be a tensor on a HIP device (got %s)" % (what, getattr(t, "device", type(t))))
+    if t.dtype != dtype or not t.is_contiguous():
+        raise RuntimeError("%s must be contiguous %s (got %s, contiguous=%s)" % (what, dtype, t.dtype, t.is_contiguous()))
+    return t.data_ptr()
+
+
+def mmd_workspace_bytes(nx, ny, d, reps):
+    return int(lib().pfm_mmd_workspace_bytes(int(nx), int(ny), int(d), int(reps)))
+
+
+def moments_workspace_bytes(nr, nf, d, reps):
+    return int(lib().pfm_moments_workspace_bytes(int(nr), int(nf), int(d), int(reps)))
+
+
+def mmd(X, Y, idx_x, idx_y, reps, median, out, ws):
+    """enqueue `reps` MMD replicates on the current stream; idx_x / idx_y are flat int32 device views
+    [reps * nx] / [reps * ny]; median / out are float64 device views of `reps` elements"""
+    nx, d = X.shape
+    ny = Y.shape[0]
+    assert idx_x.numel() == reps * nx and idx_y.numel() == reps * ny and median.numel() == reps == out.numel()
+    st = lib().pfm_mmd(torch.cuda.current_stream().cuda_stream, _ptr(X, torch.float64, "X"), nx, _ptr(Y, torch.float64, "Y"),
+                       ny, d, _ptr(idx_x, torch.int32, "idx_x"), _ptr(idx_y, torch.int32, "idx_y"), int(reps),
+                       _ptr(median, torch.float64, "median"), _ptr(out, torch.float64, "mmd"), _ptr(ws, torch.uint8, "workspace"),
+                       ws.numel())
+    check(st, "pfm_mmd")
+
+
+def boot_moments(Xr, Xf, idx_r, idx_f, reps, mean, cov, ws):
+    """enqueue the bootstrap means [reps, 2, d] and covariances [reps, 2, d, d] on the current stream"""
+    nr, d = Xr.shape
+    nf = Xf.shape[0]
+    assert idx_r.numel() == reps * nr and idx_f.numel() == reps * nf
+    assert mean.numel() == reps * 2 * d and cov.numel() == reps * 2 * d * d
+    st = lib().pfm_boot_moments(torch.cuda.current_stream().cuda_stream, _ptr(Xr, torch.float64, "X_real"), nr,
+                                _ptr(Xf, torch.float64, "X_fake"), nf, d, _ptr(idx_r, torch.int32, "idx_real"),
+                                _ptr(idx_f, torch.int32, "idx_fake"), int(reps), _ptr(mean, torch.float64, "mean"),
+                                _ptr(cov, torch.float64, "cov"), _ptr(ws, torch.uint8, "workspace"), ws.numel())
+    check(st, "pfm_boot_moments")

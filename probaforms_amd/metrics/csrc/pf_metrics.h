@@ -1,0 +1,80 @@
+/*
+ * pf_metrics.h -- C ABI of libpf_metrics.so: bootstrapped two-sample metrics of
+ * probaforms.metrics on the MI355X (gfx950).
+ *
+ *   pfm_mmd           one maximum-mean-discrepancy replicate per bootstrap draw
+ *                     (probaforms/metrics/mmd.py, mmd_calc): median pairwise distance by
+ *                     radix select, then the RBF kernel means over XX, YY and XY
+ *   pfm_boot_moments  mean and np.cov covariance (ddof 1) of each resampled set
+ *                     (probaforms/metrics/fd.py); the trace of the matrix square root is
+ *                     left to the caller
+ *
+ * Conventions (as include/rnvp_hip.h)
+ *   - every pointer is a DEVICE pointer; sizes are plain integers;
+ *   - the caller owns all device memory including the workspace (no hidden hipMalloc);
+ *     *_workspace_bytes() says how much a call needs;
+ *   - kernels are enqueued on `stream` (a hipStream_t passed as void*) and the call
+ *     returns without synchronising;
+ *   - return value: 0 ok; <0 argument error (PFM_E*); >0 a hipError_t;
+ *   - no global mutable state.  Reductions run in a fixed order with no float atomics:
+ *     the same inputs give bitwise the same outputs.
+ *
+ * Data layout
+ *   X [nx, d], Y [ny, d]: float64 row-major.
+ *   idx_x [reps, nx], idx_y [reps, ny]: int32 bootstrap indices, replicate r resamples row
+ *   idx_x[r * nx + i] of X as its row i (sklearn.utils.resample; never materialised).
+ */
+#ifndef PF_METRICS_H
+#define PF_METRICS_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define PFM_OK            0
+#define PFM_EINVAL       (-1)   /* NULL pointer, non-positive size, index range       */
+#define PFM_EUNSUPPORTED (-2)   /* d too large for the moments kernels' LDS row tile    */
+#define PFM_EWORKSPACE   (-3)   /* workspace smaller than *_workspace_bytes() says      */
+
+#define PFM_VERSION 100         /* pfm_version(): bumped whenever an argument list changes */
+
+#define PFM_MOMENTS_MAX_D 4096  /* one centred row must fit the 32 KB LDS row tile      */
+
+int         pfm_version(void);
+const char *pfm_status_string(int status);
+
+/* bytes of workspace pfm_mmd needs for `reps` replicates of an nx + ny row pooled sample */
+size_t pfm_mmd_workspace_bytes(int64_t nx, int64_t ny, int64_t d, int64_t reps);
+
+/*
+ * `reps` MMD replicates.  For replicate r, with Z = [X[idx_x[r]]; Y[idx_y[r]]] (m = nx + ny rows):
+ *   median[r] = np.median of the m x m Euclidean distance matrix of Z (its m diagonal zeros
+ *               and every pair i < j twice included): the mean of the order statistics of rank
+ *               (m*m - 1) / 2 and m*m / 2, selected exactly among the kernel's own d^2 values;
+ *   mmd[r]    = mean K_XX + mean K_YY - 2 mean K_XY,  K = exp(-gamma d^2), gamma = 1 / (2 median^2),
+ *               diagonals of K_XX and K_YY included.
+ * A replicate whose median is 0 gets mmd = NaN (the reference raises; the caller checks `median`).
+ */
+int pfm_mmd(void *stream, const double *X, int64_t nx, const double *Y, int64_t ny, int64_t d,
+            const int32_t *idx_x, const int32_t *idx_y, int64_t reps,
+            double *median, double *mmd, void *workspace, size_t workspace_bytes);
+
+/* bytes of workspace pfm_boot_moments needs */
+size_t pfm_moments_workspace_bytes(int64_t nr, int64_t nf, int64_t d, int64_t reps);
+
+/*
+ * Mean and covariance (np.cov(rowvar=False), ddof 1, two passes: the mean, then the centred
+ * products) of each resampled set: job j = 2 r + s, s = 0 for Xr[idx_r[r]], 1 for Xf[idx_f[r]].
+ *   mean [reps, 2, d]      cov [reps, 2, d, d] (symmetric, both triangles written)
+ */
+int pfm_boot_moments(void *stream, const double *Xr, int64_t nr, const double *Xf, int64_t nf, int64_t d,
+                     const int32_t *idx_r, const int32_t *idx_f, int64_t reps,
+                     double *mean, double *cov, void *workspace, size_t workspace_bytes);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

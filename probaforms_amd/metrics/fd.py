@@ -1,0 +1,77 @@
+"""frechet_distance: probaforms/metrics/fd.py with the bootstrap moments on the GPU (csrc/pf_metrics.hip,
+pfm_boot_moments) and the trace of the matrix square root on the host."""
+import numpy as np
+import torch
+
+from . import _boot, _lib
+
+
+def trace_sqrtm(A, B):
+    """tr sqrtm(A @ B) for symmetric positive semi-definite A, B (numpy only).  With S = sqrt(A) (eigh), A B
+    is similar to S B S, whose eigenvalues are real and >= 0: the trace is sum sqrt(clip(eigvalsh(S B S), 0)).
+    Agrees with scipy.linalg.sqrtm(A @ B).real.trace() to rounding, also for singular A (n < d)."""
+    w, V = np.linalg.eigh(A)
+    S = (V * np.sqrt(np.clip(w, 0.0, None))) @ V.T
+    M = S @ B @ S
+    ev = np.linalg.eigvalsh((M + M.T) * 0.5)
+    return float(np.sum(np.sqrt(np.clip(ev, 0.0, None))))
+
+
+def frechet_distance(X_real, X_fake, n_iters=100, standardize=False):
+    '''
+    Calculates the Frechet Distance between real and fake samples, bootstrapped.
+
+    Same signature, defaults, random stream and return value as the reference: per iteration the rows of
+    X_real, then of X_fake, are resampled with replacement from numpy's global generator;
+    FD = ||mu_r - mu_f||^2 + tr S_r + tr S_f - 2 tr sqrtm(S_r S_f), S the np.cov covariance (ddof 1).
+
+    Parameters:
+    -----------
+    X_real: array of shape [n_samples, n_features] (numpy, array-like or torch; a CUDA tensor stays on the device)
+        Real sample.
+    X_fake: array of shape [m_samples, n_features]
+        Generated sample.
+    n_iters: int
+        The number of bootstrap iterations. Default = 100.
+    standardize: boolean
+        If True, the mean and population std of X_real standardise both samples. Default = False.
+
+    Return:
+    -------
+    (mean, std) of the replicates' distance (np.std, ddof 0), numpy float64.
+    '''
+    frd = replicates(X_real, X_fake, n_iters, standardize)
+    return frd.mean(axis=0), frd.std(axis=0)
+
+
+def replicates(X_real, X_fake, n_iters=100, standardize=False):
+    """-> numpy float64 [n_iters]: each bootstrap replicate's Frechet distance, the draws of the public call"""
+    mean, cov = moments(X_real, X_fake, n_iters, standardize)
+    frd = np.empty(n_iters)
+    for i in range(n_iters):
+        diff = np.sum((mean[i, 0] - mean[i, 1]) ** 2.0)
+        frd[i] = diff + np.trace(cov[i, 0]) + np.trace(cov[i, 1]) - 2 * trace_sqrtm(cov[i, 0], cov[i, 1])
+    return frd
+
+
+def moments(X_real, X_fake, n_iters=100, standardize=False):
+    """-> (mean [n_iters, 2, d], cov [n_iters, 2, d, d]) of the resampled real (0) and fake (1) sets, numpy float64"""
+    Xr, Xf = _boot.prepare(X_real, X_fake, ("X_real", "X_fake"), n_iters)
+    nr, d = Xr.shape
+    nf = Xf.shape[0]
+    if d > _lib.MOMENTS_MAX_D:
+        raise ValueError("frechet_distance supports at most %d features, got %d" % (_lib.MOMENTS_MAX_D, d))
+    with torch.cuda.device(Xr.device):
+        if standardize:
+            Xr, Xf = _boot.standardize(Xr, Xf)
+        per_rep = _lib.moments_workspace_bytes(nr, nf, d, 1)
+        sizes = _boot.group_sizes(n_iters, nr + nf, per_rep)
+        ws = torch.empty(max(_lib.moments_workspace_bytes(nr, nf, d, r) for r in sizes), dtype=torch.uint8, device=Xr.device)
+        mean = torch.empty((n_iters, 2, d), dtype=torch.float64, device=Xr.device)
+        cov = torch.empty((n_iters, 2, d, d), dtype=torch.float64, device=Xr.device)
+
+        def launch(start, reps, ir, jf):
+            _lib.boot_moments(Xr, Xf, ir, jf, reps, mean[start:start + reps], cov[start:start + reps], ws)
+
+        _boot.run_groups(n_iters, nr, nf, Xr.device, launch, per_rep)
+        return mean.cpu().numpy(), cov.cpu().numpy()
