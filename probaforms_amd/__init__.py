@@ -5,8 +5,9 @@
 
 Only the path named in BASELINE.json is implemented: the affine
 coupling stack forward/inverse/backward as hand-written HIP kernels behind the reference's
-sklearn-style ``RealNVP.fit(X, C)`` / ``.sample(C)`` API, and the two multivariate metrics of
-``probaforms.metrics`` (MMD, Frechet distance) on their own HIP library.  There is no CPU fallback.
+sklearn-style ``RealNVP.fit(X, C)`` / ``.sample(C)`` API, the CVAE, the ConditionalWGAN (training and
+sampling kernels in their own HIP library), and the two multivariate metrics of ``probaforms.metrics``
+(MMD, Frechet distance) on their own HIP library.  There is no CPU fallback.
 """
 __version__ = "0.1.0"
 
@@ -21,7 +22,7 @@ def install_as_probaforms():
     import sys
     import types
     from . import models
-    from .models import cvae, interfaces, nflow, realnvp
+    from .models import cvae, interfaces, nflow, realnvp, wgan
     existing = sys.modules.get("probaforms")
     if existing is not None and getattr(existing, "__probaforms_amd__", False) is False:
         raise RuntimeError("a different `probaforms` package is already imported (%s)"
@@ -39,6 +40,6 @@ def install_as_probaforms():
     sys.modules["probaforms.metrics"] = met
     sys.modules["probaforms"] = pkg
     sys.modules["probaforms.models"] = models
-    for name, mod in (("realnvp", realnvp), ("nflow", nflow), ("interfaces", interfaces), ("cvae", cvae)):
+    for name, mod in (("realnvp", realnvp), ("nflow", nflow), ("interfaces", interfaces), ("cvae", cvae), ("wgan", wgan)):
         sys.modules["probaforms.models." + name] = mod
     return pkg

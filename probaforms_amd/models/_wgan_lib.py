@@ -1,0 +1,184 @@
+"""ctypes binding of libpf_wgan.so (C ABI: probaforms_amd/models/wgan_csrc/pf_wgan.h).
+
+The library is built in-tree by `make -C probaforms_amd/models/wgan_csrc` (see __graft_entry__.build) and loaded on the
+first call, so importing probaforms_amd.models.wgan needs no GPU.  There is NO fallback: a missing library, a shape the
+kernels do not support or a tensor off the HIP device raises.
+"""
+import ctypes as C
+import os
+import threading
+
+import torch
+
+ABI_VERSION = 100          # pfw_version() of the library this binding matches (pf_wgan.h PFW_VERSION)
+MAX_HIDDEN = 8             # PFW_MAX_HIDDEN
+ACT_TANH, ACT_RELU = 0, 1  # PFW_ACT_*
+NET_G, NET_D = 0, 1        # PFW_NET_*
+STEP_GEN, STEP_CRITIC = 0, 1   # PFW_STEP_*
+EUNSUPPORTED = -2
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "wgan_csrc", "libpf_wgan.so")
+
+
+class Shape(C.Structure):
+    """pfw_shape"""
+    _fields_ = [("d", C.c_int32), ("c", C.c_int32), ("latent", C.c_int32),
+                ("g_n_hidden", C.c_int32), ("g_hidden", C.c_int32 * MAX_HIDDEN), ("g_act", C.c_int32),
+                ("d_n_hidden", C.c_int32), ("d_hidden", C.c_int32 * MAX_HIDDEN), ("d_act", C.c_int32)]
+
+    @classmethod
+    def make(cls, d, c, latent, g_hidden, d_hidden, g_act, d_act):
+        g_hidden, d_hidden = [int(h) for h in g_hidden], [int(h) for h in d_hidden]
+        for h in (g_hidden, d_hidden):
+            if not 1 <= len(h) <= MAX_HIDDEN:
+                raise ValueError("ConditionalWGAN on the GPU supports 1..%d hidden layers per net (got %d)" % (MAX_HIDDEN, len(h)))
+        s = cls()
+        s.d, s.c, s.latent = int(d), int(c), int(latent)
+        s.g_n_hidden, s.d_n_hidden = len(g_hidden), len(d_hidden)
+        for i, h in enumerate(g_hidden):
+            s.g_hidden[i] = h
+        for i, h in enumerate(d_hidden):
+            s.d_hidden[i] = h
+        s.g_act = ACT_TANH if g_act == 'tanh' else ACT_RELU          # wgan.py:26-32: anything else is ReLU
+        s.d_act = ACT_TANH if d_act == 'tanh' else ACT_RELU
+        return s
+
+
+class RMSprop(C.Structure):
+    """pfw_rmsprop"""
+    _fields_ = [("lr", C.c_double), ("alpha", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
+                ("clamp", C.c_double)]
+
+
+_VP, _I64, _SZ, _SP, _OP = C.c_void_p, C.c_int64, C.c_size_t, C.POINTER(Shape), C.POINTER(RMSprop)
+
+_SIGNATURES = {
+    "pfw_version": (C.c_int, []),
+    "pfw_status_string": (C.c_char_p, [C.c_int]),
+    "pfw_param_count": (_I64, [_SP, C.c_int]),
+    "pfw_workspace_bytes": (_SZ, [_SP, _I64, _I64]),
+    "pfw_generate": (C.c_int, [_VP, _SP, _VP, _VP, _VP, _I64, _VP]),
+    "pfw_critic": (C.c_int, [_VP, _SP, _VP, _VP, _VP, _I64, _VP]),
+    "pfw_loss_grad": (C.c_int, [_VP, _SP, C.c_int, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _SZ]),
+    "pfw_train_step": (C.c_int, [_VP, _SP, C.c_int, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _OP, _VP, _VP, _VP, _SZ]),
+    "pfw_fit_epoch": (C.c_int, [_VP, _SP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _I64, _VP, _OP, _VP, _VP, _SZ]),
+    "pfw_epoch_losses": (C.c_int, [_VP, _SP, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _SZ]),
+}
+EXPORTS = tuple(_SIGNATURES)
+
+_lib = None
+_lock = threading.Lock()
+
+
+class WganLibraryMissing(RuntimeError):
+    pass
+
+
+def lib():
+    """Load libpf_wgan.so once; raise loudly if it has not been built or is another ABI version."""
+    global _lib
+    if _lib is None:
+        with _lock:
+            if _lib is None:
+                if not os.path.exists(LIB_PATH):
+                    raise WganLibraryMissing(
+                        "%s not found: build it with `make -C probaforms_amd/models/wgan_csrc` "
+                        "(or `python -c 'import __graft_entry__ as g; g.build()'`). "
+                        "ConditionalWGAN has no CPU fallback." % LIB_PATH)
+                L = C.CDLL(LIB_PATH)
+                L.pfw_version.restype, L.pfw_version.argtypes = C.c_int, []
+                have = int(L.pfw_version())
+                if have != ABI_VERSION:
+                    raise WganLibraryMissing("%s reports pfw_version() = %d, this binding is written for %d: rebuild it "
+                                             "(`make -C probaforms_amd/models/wgan_csrc`)" % (LIB_PATH, have, ABI_VERSION))
+                for name, (res, args) in _SIGNATURES.items():
+                    fn = getattr(L, name)
+                    fn.restype, fn.argtypes = res, args
+                _lib = L
+    return _lib
+
+
+def check(status, what):
+    if status != 0:
+        msg = lib().pfw_status_string(status)
+        raise RuntimeError("%s failed: %s (status %d)" % (what, msg.decode() if msg else "?", status))
+
+
+def _ptr(t, dtype, what, nullable=False):
+    if t is None:
+        if nullable:
+            return None
+        raise RuntimeError("%s is required" % what)
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError("%s must be a tensor on a HIP device (got %s)" % (what, getattr(t, "device", type(t))))
+    if t.dtype != dtype or not t.is_contiguous():
+        raise RuntimeError("%s must be contiguous %s (got %s, contiguous=%s)" % (what, dtype, t.dtype, t.is_contiguous()))
+    return t.data_ptr()
+
+
+def _f32(t, what, nullable=False):
+    return _ptr(t, torch.float32, what, nullable)
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def param_count(shape, net):
+    n = int(lib().pfw_param_count(C.byref(shape), int(net)))
+    if n < 0:
+        raise ValueError("invalid ConditionalWGAN shape")
+    return n
+
+
+def workspace_bytes(shape, batch_rows, loss_rows=0):
+    return int(lib().pfw_workspace_bytes(C.byref(shape), int(batch_rows), int(loss_rows)))
+
+
+def rmsprop(lr, alpha=0.99, eps=1e-8, weight_decay=0.0, clamp=0.0):
+    return RMSprop(float(lr), float(alpha), float(eps), float(weight_decay), float(clamp))
+
+
+def generate(shape, params, z, c, n, out):
+    """out [n, d] = G([z || c]) on the current stream (inference only: no autograd)"""
+    check(lib().pfw_generate(_stream(), C.byref(shape), _f32(params, "params"), _f32(z, "z"), _f32(c, "C", True), int(n),
+                             _f32(out, "out")), "pfw_generate")
+
+
+def critic(shape, params, x, c, n, out):
+    """out [n] = D([x || c]) on the current stream (inference only: no autograd)"""
+    check(lib().pfw_critic(_stream(), C.byref(shape), _f32(params, "params"), _f32(x, "X"), _f32(c, "C", True), int(n),
+                           _f32(out, "out")), "pfw_critic")
+
+
+def loss_grad(shape, kind, params, x, c, row_index, z, rows, grad_out, loss_out, ws):
+    check(lib().pfw_loss_grad(_stream(), C.byref(shape), int(kind), _f32(params, "params"), _f32(x, "X"), _f32(c, "C", True),
+                              _ptr(row_index, torch.int64, "row_index", True), _f32(z, "z"), int(rows),
+                              _f32(grad_out, "grad_out", True), _f32(loss_out, "loss_out", True),
+                              _ptr(ws, torch.uint8, "workspace"), ws.numel()), "pfw_loss_grad")
+
+
+def train_step(shape, kind, params, square_avg, x, c, row_index, z, rows, opt, grad_out, loss_out, ws):
+    check(lib().pfw_train_step(_stream(), C.byref(shape), int(kind), _f32(params, "params"), _f32(square_avg, "square_avg"),
+                               _f32(x, "X"), _f32(c, "C", True), _ptr(row_index, torch.int64, "row_index", True), _f32(z, "z"),
+                               int(rows), C.byref(opt), _f32(grad_out, "grad_out", True), _f32(loss_out, "loss_out", True),
+                               _ptr(ws, torch.uint8, "workspace"), ws.numel()), "pfw_train_step")
+
+
+def fit_epoch(shape, params, square_avg, x, c, perm, z_batches, z_full, n, batch_size, kinds, opt, epoch_losses, ws):
+    """kinds: a host int8 numpy array, one PFW_STEP_* per batch"""
+    import numpy as np
+    kinds = np.ascontiguousarray(kinds, dtype=np.int8)
+    assert kinds.size == -(-int(n) // int(batch_size))
+    check(lib().pfw_fit_epoch(_stream(), C.byref(shape), _f32(params, "params"), _f32(square_avg, "square_avg"), _f32(x, "X"),
+                              _f32(c, "C", True), _ptr(perm, torch.int64, "perm"), _f32(z_batches, "z_batches"),
+                              _f32(z_full, "z_full", True), int(n), int(batch_size), kinds.ctypes.data, C.byref(opt),
+                              _f32(epoch_losses, "epoch_losses", True), _ptr(ws, torch.uint8, "workspace"), ws.numel()),
+          "pfw_fit_epoch")
+
+
+def epoch_losses(shape, params, x, c, z_full, n, out, ws):
+    check(lib().pfw_epoch_losses(_stream(), C.byref(shape), _f32(params, "params"), _f32(x, "X"), _f32(c, "C", True),
+                                 _f32(z_full, "z_full"), int(n), _f32(out, "epoch_losses"), _ptr(ws, torch.uint8, "workspace"),
+                                 ws.numel()), "pfw_epoch_losses")
