@@ -6,8 +6,9 @@
 Only the path named in BASELINE.json is implemented: the affine
 coupling stack forward/inverse/backward as hand-written HIP kernels behind the reference's
 sklearn-style ``RealNVP.fit(X, C)`` / ``.sample(C)`` API, the CVAE, the ConditionalWGAN (training and
-sampling kernels in their own HIP library), and the two multivariate metrics of ``probaforms.metrics``
-(MMD, Frechet distance) on their own HIP library.  There is no CPU fallback.
+sampling kernels in their own HIP library), and the metrics of ``probaforms.metrics`` on their own HIP library:
+the two multivariate ones (MMD, Frechet distance) and the eight 1-D ones in ``probaforms_amd.metrics.ks1d`` and
+``probaforms_amd.metrics.div1d``.  There is no CPU fallback.
 """
 __version__ = "0.1.0"
 
@@ -16,8 +17,9 @@ def install_as_probaforms():
     """Make `from probaforms.models import RealNVP` (the reference's import path, README.md:48) and
     `from probaforms import metrics` resolve to this package: registers `probaforms`, `probaforms.models`, the
     model modules and `probaforms.metrics` in sys.modules.  `probaforms.metrics` exports exactly
-    maximum_mean_discrepancy and frechet_distance: the reference's 1-D metrics are not provided, so importing
-    one of them (e.g. kolmogorov_smirnov_1d) raises ImportError.
+    maximum_mean_discrepancy and frechet_distance: the reference's 1-D metrics are served from
+    probaforms_amd.metrics.ks1d / div1d only, so importing one of them (e.g. kolmogorov_smirnov_1d) from
+    probaforms.metrics raises ImportError.
     Call it before anything imports the reference; it refuses to shadow an already imported one."""
     import sys
     import types

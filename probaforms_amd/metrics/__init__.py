@@ -1,4 +1,4 @@
-"""probaforms_amd.metrics -- the two multivariate metrics of probaforms.metrics on the GPU.
+"""probaforms_amd.metrics -- the metrics of probaforms.metrics on the GPU.
 
     from probaforms_amd.metrics import maximum_mean_discrepancy, frechet_distance
     mu, sigma = maximum_mean_discrepancy(X, Y, n_iters=100, standardize=False)
@@ -10,10 +10,14 @@ arrays, array-likes or torch tensors; a CUDA tensor is used on its device withou
 The hot paths are HIP kernels in libpf_metrics.so (csrc/), loaded on the first call, so importing this
 module needs no GPU.  There is no CPU fallback.
 
-Only these two metrics exist here.  The eight 1-D metrics of the reference (kolmogorov_smirnov_1d,
-cramer_von_mises_1d, anderson_darling_1d, roc_auc_score_1d, kullback_leibler_1d[_kde],
-jensen_shannon_1d[_kde]) are not provided: `from probaforms.metrics import kolmogorov_smirnov_1d` after
-`probaforms_amd.install_as_probaforms()` raises ImportError.
+The eight 1-D metrics of the reference live in the reference's module paths, not in this package's export list:
+
+    from probaforms_amd.metrics.ks1d import kolmogorov_smirnov_1d, cramer_von_mises_1d, roc_auc_score_1d, anderson_darling_1d
+    from probaforms_amd.metrics.div1d import kullback_leibler_1d, jensen_shannon_1d           # histograms, bins=10
+    from probaforms_amd.metrics.div1d import kullback_leibler_1d_kde, jensen_shannon_1d_kde   # Gaussian KDE, bins=101
+
+`__all__` and the `probaforms.metrics` alias (`probaforms_amd.install_as_probaforms()`) name only the two
+multivariate metrics, so `from probaforms.metrics import kolmogorov_smirnov_1d` raises ImportError there.
 """
 from .fd import frechet_distance
 from .mmd import maximum_mean_discrepancy

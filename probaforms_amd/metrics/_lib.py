@@ -10,8 +10,12 @@ import threading
 
 import torch
 
-ABI_VERSION = 100          # pfm_version() of the library this binding matches (pf_metrics.h PFM_VERSION)
+ABI_VERSION = 101          # pfm_version() of the library this binding matches (pf_metrics.h PFM_VERSION)
 MOMENTS_MAX_D = 4096       # PFM_MOMENTS_MAX_D
+# pfm_metric1d's statistics (pf_metrics.h PFM_M1D_*)
+M1D_KS, M1D_CVM, M1D_AD, M1D_AUC, M1D_HIST, M1D_KDE = range(6)
+CVM_MAX_N = 1 << 20        # pooled rows pfm_metric1d's Cramer-von Mises sums hold exactly
+PFM_EUNSUPPORTED, PFM_EWORKSPACE = -2, -3
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libpf_metrics.so")
@@ -25,6 +29,9 @@ _SIGNATURES = {
     "pfm_mmd": (C.c_int, [_VP, _VP, _I64, _VP, _I64, _I64, _VP, _VP, _I64, _VP, _VP, _VP, _SZ]),
     "pfm_moments_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64]),
     "pfm_boot_moments": (C.c_int, [_VP, _VP, _I64, _VP, _I64, _I64, _VP, _VP, _I64, _VP, _VP, _VP, _SZ]),
+    "pfm_metric1d_workspace_bytes": (_SZ, [C.c_int, _I64, _I64, _I64, _I64, _I64]),
+    "pfm_metric1d": (C.c_int, [_VP, C.c_int, _VP, _VP, _VP, _VP, _I64, _I64, _I64, _VP, _VP, _I64, _I64, C.c_double,
+                               C.c_double, _VP, _VP, _SZ]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -106,3 +113,24 @@ def boot_moments(Xr, Xf, idx_r, idx_f, reps, mean, cov, ws):
                                 _ptr(idx_f, torch.int32, "idx_fake"), int(reps), _ptr(mean, torch.float64, "mean"),
                                 _ptr(cov, torch.float64, "cov"), _ptr(ws, torch.uint8, "workspace"), ws.numel())
     check(st, "pfm_boot_moments")
+
+
+def metric1d_workspace_bytes(metric, nr, nf, d, reps, bins):
+    return int(lib().pfm_metric1d_workspace_bytes(int(metric), int(nr), int(nf), int(d), int(reps), int(bins)))
+
+
+def metric1d_status(metric, cols, perm, gstart, ngroups, nr, nf, idx_r, idx_f, reps, bins, h_r, h_f, out, ws):
+    """enqueue `reps` replicates of one pfm_metric1d statistic on the current stream and return the status; cols /
+    perm / gstart / ngroups describe the pooled columns (pf_metrics.h), `out` is the statistic's output view"""
+    d = cols.shape[0]
+    assert idx_r.numel() == reps * nr and idx_f.numel() == reps * nf and cols.shape[1] == nr + nf
+    return int(lib().pfm_metric1d(torch.cuda.current_stream().cuda_stream, int(metric), _ptr(cols, torch.float64, "cols"),
+                                  _ptr(perm, torch.int32, "perm"), _ptr(gstart, torch.int32, "gstart"),
+                                  _ptr(ngroups, torch.int32, "ngroups"), int(nr), int(nf), int(d),
+                                  _ptr(idx_r, torch.int32, "idx_real"), _ptr(idx_f, torch.int32, "idx_fake"), int(reps),
+                                  int(bins), float(h_r), float(h_f), _ptr(out, out.dtype, "out"), _ptr(ws, torch.uint8, "workspace"),
+                                  ws.numel()))
+
+
+def metric1d(*args):
+    check(metric1d_status(*args), "pfm_metric1d")

@@ -8,6 +8,9 @@
  *   pfm_boot_moments  mean and np.cov covariance (ddof 1) of each resampled set
  *                     (probaforms/metrics/fd.py); the trace of the matrix square root is
  *                     left to the caller
+ *   pfm_metric1d      the per-feature rank and density statistics behind the eight 1-D
+ *                     metrics (probaforms/metrics/ks1d.py, div1d.py), from the pooled
+ *                     column's sorted order and the replicate's draw counts
  *
  * Conventions (as include/rnvp_hip.h)
  *   - every pointer is a DEVICE pointer; sizes are plain integers;
@@ -39,7 +42,7 @@ extern "C" {
 #define PFM_EUNSUPPORTED (-2)   /* d too large for the moments kernels' LDS row tile    */
 #define PFM_EWORKSPACE   (-3)   /* workspace smaller than *_workspace_bytes() says      */
 
-#define PFM_VERSION 100         /* pfm_version(): bumped whenever an argument list changes */
+#define PFM_VERSION 101         /* pfm_version(): bumped whenever an argument list changes */
 
 #define PFM_MOMENTS_MAX_D 4096  /* one centred row must fit the 32 KB LDS row tile      */
 
@@ -73,6 +76,43 @@ size_t pfm_moments_workspace_bytes(int64_t nr, int64_t nf, int64_t d, int64_t re
 int pfm_boot_moments(void *stream, const double *Xr, int64_t nr, const double *Xf, int64_t nf, int64_t d,
                      const int32_t *idx_r, const int32_t *idx_f, int64_t reps,
                      double *mean, double *cov, void *workspace, size_t workspace_bytes);
+
+/* ---- 1-D metrics (pf_metrics1d.hip) ------------------------------------------------------ */
+
+/* what pfm_metric1d writes per (replicate r, feature f); rf = r * d + f */
+#define PFM_M1D_KS    0   /* double  out[rf]: the ks_2samp statistic                              */
+#define PFM_M1D_CVM   1   /* int64   out[2 rf + s]: sum_i (2 R_i - 2 i)^2 over sample s's sorted
+                             rows (R the pooled average rank, i = 1..n_s); pooled N <= 2^20        */
+#define PFM_M1D_AD    2   /* double  out[3 rf + s]: scipy's midrank `inner` summed over the distinct
+                             pooled values for sample s; out[3 rf + 2]: the number of those values */
+#define PFM_M1D_AUC   3   /* int64   out[rf]: 2 U, U = pairs (real, fake) with fake > real, ties 1/2 */
+#define PFM_M1D_HIST  4   /* int32   out[(2 rf + s) bins + k]: np.histogram counts of sample s in
+                             the bins of np.histogram(pooled, bins)                               */
+#define PFM_M1D_KDE   5   /* double  out[(2 rf + s) bins + k]: log sum_i exp(-(x_k - v_i)^2 / (2 h_s^2))
+                             over sample s's resampled values v_i, x = linspace(min, max, bins) of
+                             the pooled replicate; the caller adds the kernel norm and -log n_s   */
+
+/* bytes of workspace pfm_metric1d needs (0: the arguments are invalid) */
+size_t pfm_metric1d_workspace_bytes(int metric, int64_t nr, int64_t nf, int64_t d, int64_t reps, int64_t bins);
+
+/*
+ * `reps` replicates of one 1-D statistic, every feature.  N = nr + nf pooled rows: real rows
+ * 0 .. nr-1, fake rows nr .. N-1.  Per call (not per replicate) the caller provides, per feature f:
+ *   cols    [d, N] float64   the pooled original column f
+ *   perm    [d, N] int32     pooled rows in ascending order of cols[f]
+ *   gstart  [d, N + 1] int32 tie groups (runs of equal values) of that order: group g is sorted
+ *                            positions gstart[f, g] .. gstart[f, g + 1] - 1, g < ngroups[f];
+ *                            gstart[f, ngroups[f]] = N
+ *   ngroups [d] int32
+ * idx_r [reps, nr] / idx_f [reps, nf] are the bootstrap indices (as pfm_boot_moments); `bins`
+ * matters for HIST / KDE, h_r / h_f (the samples' bandwidths) for KDE only.  `out` is laid out
+ * as the PFM_M1D_* comment says; HIST zeroes its counts itself.
+ * Returns PFM_EUNSUPPORTED for CVM with N > 2^20.
+ */
+int pfm_metric1d(void *stream, int metric, const double *cols, const int32_t *perm, const int32_t *gstart,
+                 const int32_t *ngroups, int64_t nr, int64_t nf, int64_t d, const int32_t *idx_r,
+                 const int32_t *idx_f, int64_t reps, int64_t bins, double h_r, double h_f, void *out,
+                 void *workspace, size_t workspace_bytes);
 
 #ifdef __cplusplus
 }
