@@ -215,7 +215,16 @@ static int fit_epoch_dp_impl(void *stream, rnvp_all_reduce_fn all_reduce, void *
     // batch's rnvp_loss_grad, then re-packed by every batch's Adam launch (rnvp::mfma::adam_pack)
     const bool chained = rnvp::mfma::train_supported(ks);
     const int nchunks = (chained && chunks > 1) ? (chunks < ks.L ? chunks : ks.L) : 1;
+    // The error word in the workspace is cleared by the pack launch of this rank's first training step; a rank whose share is empty
+    // from the first batch on reaches its Adam launches without one, so the word is cleared here (a stale non-zero word would make
+    // this rank alone skip Adam: replicas that drift apart silently).  packed_valid is set only once THIS rank has packed in this
+    // call: conservative -- with the word clear an empty-share step's finish launch does re-pack -- at the price of one redundant pack
+    // launch at such a rank's first batch with rows
     bool packed_valid = false;
+    if (chained && n > 0) {
+        rc = rnvp::mfma::clear_error(st, ks, workspace, workspace_bytes);
+        if (rc) return rc;
+    }
     int64_t k = 0;
     for (int64_t s0 = 0; s0 < n; s0 += batch_size, ++k) {
         const int64_t rows = (n - s0 < batch_size) ? n - s0 : batch_size;
@@ -267,7 +276,7 @@ static int fit_epoch_dp_impl(void *stream, rnvp_all_reduce_fn all_reduce, void *
                                                   exp_avg_sq, ak, workspace, workspace_bytes, l0, l1 - l0);
                 if (rc) return rc;
             }
-            packed_valid = true;
+            if (mine > 0) packed_valid = true;
             continue;
         }
         if (chained && mine > 0) {
@@ -287,7 +296,7 @@ static int fit_epoch_dp_impl(void *stream, rnvp_all_reduce_fn all_reduce, void *
             if (!exp_avg || !exp_avg_sq) return RNVP_EINVAL;
             rc = rnvp::mfma::adam_pack(st, ks, params, grad_loss, grad_loss + P, loss_hist + k, exp_avg, exp_avg_sq,
                                        rnvp::make_adam(lr, beta1, beta2, eps, weight_decay, first_step + k), workspace, workspace_bytes);
-            packed_valid = true;
+            if (mine > 0) packed_valid = true;
         } else {
             rc = rnvp_dp_finish_step(stream, params, grad_loss, exp_avg, exp_avg_sq, P, lr, beta1, beta2, eps, weight_decay,
                                      first_step + k, loss_hist + k);

@@ -119,6 +119,7 @@ int train_step(hipStream_t st, const KShape &k, float *params, const float *x, c
 // the data-parallel step in chunks of layers (rnvp_dp.hip, rnvp_dp_set_chunks): training launch alone, then per chunk the partial
 // sums, [the caller's all-reduce of the chunk,] Adam + re-pack of the chunk's layers
 struct PendingPartials { int glayer_floats, w2c, grid; float inv_B; };
+int clear_error(hipStream_t st, const KShape &k, void *ws, size_t ws_bytes);
 int loss_partials(hipStream_t st, const KShape &k, const float *params, const float *x, const float *c, const int64_t *row_index,
                   int64_t n, float inv_B, void *ws, size_t ws_bytes, bool packed_valid, PendingPartials *pending);
 int finish_sum_layers(hipStream_t st, const KShape &k, const PendingPartials &p, int l0, int nl, float *grad, float *loss_out,

@@ -363,6 +363,15 @@ static bool ws_view(const KShape &k, void *ws, size_t ws_bytes, Geo *g, TrainPla
     return true;
 }
 
+// The error word is cleared by the pack launch of a rank's first training step.  A data-parallel rank whose share of the first
+// batches is empty launches no training kernel there, yet its Adam launches read the word: the epoch clears it itself, up front.
+int clear_error(hipStream_t st, const KShape &k, void *ws, size_t ws_bytes) {
+    Geo g; TrainPlan pl; WsView v;
+    if (!ws_view(k, ws, ws_bytes, &g, &pl, &v)) return RNVP_EWORKSPACE;
+    RNVP_HIP_TRY(hipMemsetAsync(error_word(v.losspart), 0, sizeof(int), st));
+    return RNVP_OK;
+}
+
 // DATA-PARALLEL step in chunks of layers (rnvp_dp.hip): the training launch alone ...
 int loss_partials(hipStream_t st, const KShape &k, const float *params, const float *x, const float *c, const int64_t *row_index,
                   int64_t n, float inv_B, void *ws, size_t ws_bytes, bool packed_valid, PendingPartials *pending) {

@@ -40,6 +40,35 @@ def _chunked_epoch_matches(rank, world):
     return bool(ok and all(torch.equal(both[0], b) for b in both))
 
 
+def _empty_share_fits(rank, world, out):
+    """chained-kernel fits in which rank 1's share of a batch is empty -- of the last batch (97 rows in batches of 32: one row left),
+    and of EVERY batch (batch_size = 1: rank 1 never launches a training kernel) -- on an engine workspace full of 0xFF bytes"""
+    from probaforms_amd import _hip
+    from probaforms_amd.models import RealNVP
+    rng = np.random.default_rng(3)
+    res = {}
+    for tag, n, bs in (("ragged", 97, 32), ("bs1", 24, 1)):
+        X = rng.standard_normal((n, 5)); C = rng.standard_normal((n, 3))
+        torch.manual_seed(0 if rank == 0 else 4321 + rank)
+        m = RealNVP(n_layers=4, hidden=(16,), batch_size=bs, n_epochs=2, lr=1e-2, weight_decay=0.05)
+        m._model_init(X, C)
+        eng = m.nf.engine()
+        assert _hip.kernel_path(eng.shape, None, _hip.OP_TRAIN) == _hip.PATH_MFMA
+        eng.workspace(_hip.OP_TRAIN, bs).fill_(0xFF)
+        m.fit(X, C)
+        flat = eng.flat.detach().clone()
+        both = [torch.empty_like(flat) for _ in range(world)]
+        dist.all_gather(both, flat)
+        res[tag + "_same"] = all(torch.equal(both[0], b) for b in both)
+        res[tag + "_flat"] = flat.cpu().numpy()
+        hist = torch.tensor([float(v) for v in m.loss_history], dtype=torch.float64)
+        hists = [torch.empty_like(hist) for _ in range(world)]
+        dist.all_gather(hists, hist)                       # every rank's own history: the empty rank's too
+        res[tag + "_hist"] = torch.stack(hists).numpy()
+    if rank == 0:
+        np.savez(out + ".empty.npz", **res)
+
+
 def main():
     out = sys.argv[1]
     dist.init_process_group("gloo")
@@ -94,6 +123,7 @@ def main():
     chunk_same = _chunked_epoch_matches(rank, world)
     if rank == 0:
         np.savez(out + ".chunks.npz", same=chunk_same)
+    _empty_share_fits(rank, world, out)
     if rank == 0:
         np.savez(out, flat=flat.cpu().numpy(), hist=np.array([float(v) for v in m.loss_history]), same=same, xs=xs,
                  cvae_flat=cflat.cpu().numpy(), cvae_hist=np.array([float(v) for v in cv.loss_history]), cvae_same=csame)

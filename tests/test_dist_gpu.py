@@ -67,6 +67,21 @@ def test_two_ranks_on_hip_kernels_match_single_process(tmp_path):
     assert np.abs(got["flat"][:ref["params_after"].size] - ref["params_after"]).max() < 2e-3
     # round 6: the exchange cut into chunks of layers gives the one-message loop's bits on both ranks
     assert bool(np.load(out + ".chunks.npz")["same"])
+    # shares that are empty (rank 1: the one-row last batch of 97 / 32; every batch at batch_size = 1), engine workspace full of 0xFF
+    # bytes on both ranks: identical replicas, finite histories, the single-process fit at the tolerances of the 1000 / 96 fit above
+    es = np.load(out + ".empty.npz")
+    rng3 = np.random.default_rng(3)
+    for tag, n3, bs3 in (("ragged", 97, 32), ("bs1", 24, 1)):
+        X3 = rng3.standard_normal((n3, 5)); C3 = rng3.standard_normal((n3, 3))
+        assert bool(es[tag + "_same"]), tag
+        assert es[tag + "_hist"].shape == (2, 2 * ((n3 + bs3 - 1) // bs3)) and np.isfinite(es[tag + "_hist"]).all(), (tag, es[tag + "_hist"])
+        assert np.array_equal(es[tag + "_hist"][0], es[tag + "_hist"][1]), tag          # (both ranks read the all-reduced loss)
+        torch.manual_seed(0)
+        m3 = RealNVP(n_layers=4, hidden=(16,), batch_size=bs3, n_epochs=2, lr=1e-2, weight_decay=0.05)
+        m3.fit(X3, C3)
+        np.testing.assert_allclose(es[tag + "_hist"][0], np.array([float(v) for v in m3.loss_history]), rtol=2e-5, atol=2e-5)
+        f3 = m3.nf.engine().flat.detach().cpu().numpy()
+        assert np.abs(es[tag + "_flat"] - f3).max() < 5e-4 and np.abs(es[tag + "_flat"] - f3).mean() < 2e-5, tag
     # sharded sampling: rank shares are consecutive blocks of the replicated draw; 'gather' rebuilds all of it
     s0, s1 = np.load(out + ".rank0.npz"), np.load(out + ".rank1.npz")
     assert s0["shard"].shape == (31, 5) and s1["shard"].shape == (30, 5)
