@@ -5,8 +5,8 @@
 
 Only the path named in BASELINE.json is implemented: the affine
 coupling stack forward/inverse/backward as hand-written HIP kernels behind the reference's
-sklearn-style ``RealNVP.fit(X, C)`` / ``.sample(C)`` API, the CVAE, the ConditionalWGAN (training and
-sampling kernels in their own HIP library), and the metrics of ``probaforms.metrics`` on their own HIP library:
+sklearn-style ``RealNVP.fit(X, C)`` / ``.sample(C)`` API, the CVAE, the ConditionalWGAN and the ConditionalNormal (training and
+sampling kernels in their own HIP libraries), and the metrics of ``probaforms.metrics`` on their own HIP library:
 the two multivariate ones (MMD, Frechet distance) and the eight 1-D ones in ``probaforms_amd.metrics.ks1d`` and
 ``probaforms_amd.metrics.div1d``.  There is no CPU fallback.
 """
@@ -24,7 +24,7 @@ def install_as_probaforms():
     import sys
     import types
     from . import models
-    from .models import cvae, interfaces, nflow, realnvp, wgan
+    from .models import cnormal, cvae, interfaces, nflow, realnvp, wgan
     existing = sys.modules.get("probaforms")
     if existing is not None and getattr(existing, "__probaforms_amd__", False) is False:
         raise RuntimeError("a different `probaforms` package is already imported (%s)"
@@ -42,6 +42,7 @@ def install_as_probaforms():
     sys.modules["probaforms.metrics"] = met
     sys.modules["probaforms"] = pkg
     sys.modules["probaforms.models"] = models
-    for name, mod in (("realnvp", realnvp), ("nflow", nflow), ("interfaces", interfaces), ("cvae", cvae), ("wgan", wgan)):
+    for name, mod in (("realnvp", realnvp), ("nflow", nflow), ("interfaces", interfaces), ("cvae", cvae), ("wgan", wgan),
+                      ("cnormal", cnormal)):
         sys.modules["probaforms.models." + name] = mod
     return pkg

@@ -128,9 +128,12 @@ class _FitDraws:
     uploads asynchronously.  At C5 (n = 1M, latent 2) an epoch needs ~4M normals: the stream, not the GPU (~2.5 ms per
     epoch), bounds the fit -- `noise_rng='device'` lifts that."""
 
-    def __init__(self, n, bounds, lat, n_epochs, device=None, slots=3):
+    def __init__(self, n, bounds, lat, n_epochs, device=None, slots=3, epoch_end=True):
+        """epoch_end=False: the model makes no full-data draw at the end of an epoch (ConditionalNormal); the third tensor of
+        next_epoch() is then empty"""
         import queue, threading
         self.n, self.bounds, self.lat, self.n_epochs = n, bounds, lat, n_epochs
+        self.epoch_end = epoch_end
         self.gen = torch.Generator()
         self.gen.set_state(torch.get_rng_state())
         pin = device is not None and torch.device(device).type == "cuda" and n * lat >= (1 << 16)
@@ -146,10 +149,11 @@ class _FitDraws:
             # the device draws of an epoch take ~1 ms; what takes time is the epoch's host randperm (12 ms at n = 1M, on the shared
             # pool): a deeper ring lets eight of them run at once (the eps buffers are device memory: 2 x n x latent floats a slot)
             slots = max(slots, 8)
+        nf = n if epoch_end else 0
         for _ in range(max(1, min(slots, n_epochs))):
             self.free.put(((torch.empty(n, dtype=torch.int64, pin_memory=pin),
                             torch.empty(n, lat, dtype=torch.float32, device=edev) if edev is not None else torch.empty(n, lat, dtype=torch.float32, pin_memory=pin),
-                            torch.empty(n, lat, dtype=torch.float32, device=edev) if edev is not None else torch.empty(n, lat, dtype=torch.float32, pin_memory=pin)), None))
+                            torch.empty(nf, lat, dtype=torch.float32, device=edev) if edev is not None else torch.empty(nf, lat, dtype=torch.float32, pin_memory=pin and nf > 0)), None))
         self.stop = False
         self.thread = threading.Thread(target=self._run, name="cvae-draws", daemon=True)
         self.thread.start()
@@ -198,12 +202,14 @@ class _FitDraws:
                         hs = HostStreamOnDevice(self.device, g).begin()
                         for (s, e) in self.bounds:
                             hs.draw(eps[s:e])
-                        hs.draw(eps_full)
+                        if self.epoch_end:
+                            hs.draw(eps_full)
                         hs.end()
                 else:
                     for (s, e) in self.bounds:
                         torch.randn(e - s, self.lat, generator=g, out=eps[s:e])
-                    torch.randn(self.n, self.lat, generator=g, out=eps_full)
+                    if self.epoch_end:
+                        torch.randn(self.n, self.lat, generator=g, out=eps_full)
                 self.ready.put((slot, fut, perm_dev))
         except BaseException as ex:               # surfaces in the consumer
             self.ready.put(ex)
