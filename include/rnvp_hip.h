@@ -237,6 +237,12 @@ int rnvp_loss_grad_zseed(void *stream, const rnvp_shape *shape,
  * (the gradient w.r.t. the conditions is not formed here: rnvp_backward_cond below).  Rows are batch rows:
  * with row_index the inputs are gathered, gz / gld / gx_out are not.  With shape->L == 1 this is the backward of one
  * RealNVPLayer.f.  Same kernels, workspace (RNVP_OP_TRAIN) and determinism as rnvp_loss_grad.
+ * `masks`: on RNVP_PATH_MFMA with a declared pattern (alt_masks 1 / 2) only the tile-split training kernel carries the per-row
+ * seeds and gx_out, and it takes at most 8192 rows per call (d <= 32; 4096 rows for wider rows; none with fewer than three
+ * 16-unit tiles in the hidden layer).  Up to there the masks pointer is not read and may be NULL, as for rnvp_loss_grad.  A
+ * call of more rows runs on the any-shape kernels, which read the table: it needs `masks` whatever alt_masks declares, and
+ * returns RNVP_EINVAL without a launch when it is NULL.  rnvp_workspace_bytes(shape, RNVP_OP_TRAIN, n_rows) covers either side.
+ * A caller that always passes its table (the Python host does) never sees the difference.
  */
 int rnvp_backward(void *stream, const rnvp_shape *shape,
                   const float *params, const uint8_t *masks,
