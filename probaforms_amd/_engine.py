@@ -523,6 +523,34 @@ class FlowEngine:
         _hip.sample(self.shape, self.params, self.masks, c, n, seed, row_offset, x, self.workspace(_hip.OP_INVERSE, n))
         return x
 
+    # -- multi-draw predictive statistics (libpf_predict.so, models/predict_csrc/pf_predict.h) ---------------
+    def predict_supported(self):
+        """whether the draw kernel holds this flow's per-tile image in LDS (else the callers run the host loop)"""
+        from .models import _predict_lib
+        return _predict_lib.supported(self.shape)
+
+    def predict_draw(self, c, n_rows, row_offset, seeds, z, n_total, k_lo, k_cnt, k_total, state=None, x_out=None,
+                     xt_out=None):
+        """x[k][r] = g(z[k][r], c[r]) for rows row_offset .. + n_rows and draws k_lo .. + k_cnt in one launch
+        (pfp_draw_accumulate) with the engine's own params, masks and shape.  seeds: k_cnt ints (counter-based prior) or
+        z [k_cnt, n_total, d] on the device.  Returns the host seed array (keep it until the stream has run)."""
+        from .models import _predict_lib
+        self.sync_params()
+        n_rows = int(n_rows)
+        c = self._cond(c, n_rows)
+        if c is not None:
+            c = c.contiguous()
+        ws = None
+        if seeds is not None:
+            nb = _predict_lib.workspace_bytes(self.shape, k_cnt)
+            if nb == 0:
+                raise _predict_lib.Unsupported("pfp_draw_accumulate: shape not supported")
+            if getattr(self, "_predict_ws", None) is None or self._predict_ws.numel() < nb:
+                self._predict_ws = torch.empty(nb, dtype=torch.uint8, device=self.device)
+            ws = self._predict_ws
+        return _predict_lib.draw_accumulate(self.shape, self.params, self.masks, c, n_rows, row_offset, seeds, z, n_total,
+                                            k_lo, k_cnt, k_total, state, x_out, xt_out, ws)
+
     def ensure_gbuf(self):
         if self.gbuf is None or self.gbuf.device != self.device:
             pad = (-(self.P + 1)) % 4

@@ -1,0 +1,185 @@
+"""Multi-draw predictive statistics of a RealNVP flow: the orchestration behind ``sample_stats`` / ``sample_many``.
+
+What the reference's notebooks do by hand (docs/examples/regression.ipynb, forecast.ipynb) --
+
+    X = np.array([model.sample(C) for _ in range(K)]);  X.mean(axis=0), X.std(axis=0), np.quantile(X, q, axis=0)
+
+-- as one call: libpf_predict.so (predict_csrc/pf_predict.h) draws the K prior samples per condition row, pushes them through
+the inverse flow and reduces across the draws on the device; only [n, d] statistics leave it.
+
+The arithmetic that needs no GPU lives here as plain functions (argument validation, the draw windows, the row chunks, the
+routing between the kernels and the host loop) so that the CPU suite covers it.
+"""
+import collections
+
+import numpy as np
+import torch
+
+Z_WINDOW_BYTES = 256 << 20        # the z buffer of a window of host-prior draws stays at or below this
+XT_CHUNK_BYTES = 1 << 30          # the transposed draws the quantile kernel sorts: above this, row chunks
+MAX_QUANTILE_DRAWS = 8192         # pf_predict.h PFP_MAX_QUANTILE_DRAWS
+
+SampleStats = collections.namedtuple("SampleStats", "mean std min max quantiles")
+
+
+def validate(n_draws, quantiles=None, ddof=0):
+    """-> (K, probs) with probs a tuple of floats or None; ValueError for n_draws < 1, a probability outside [0, 1],
+    quantiles with more than MAX_QUANTILE_DRAWS draws, or a negative ddof"""
+    if isinstance(n_draws, bool) or int(n_draws) != n_draws:
+        raise ValueError("n_draws must be an integer, got %r" % (n_draws,))
+    K = int(n_draws)
+    if K < 1:
+        raise ValueError("n_draws must be at least 1, got %d" % K)
+    if int(ddof) != ddof or int(ddof) < 0:
+        raise ValueError("ddof must be a non-negative integer, got %r" % (ddof,))
+    probs = None
+    if quantiles is not None:
+        probs = tuple(float(q) for q in np.atleast_1d(np.asarray(quantiles, dtype=np.float64)))
+        if len(probs) == 0:
+            probs = None
+    if probs is not None:
+        for q in probs:
+            if not 0.0 <= q <= 1.0:           # (NaN fails both comparisons)
+                raise ValueError("quantiles must lie in [0, 1], got %r" % (q,))
+        if K > MAX_QUANTILE_DRAWS:
+            raise ValueError("quantiles need n_draws <= %d (one series is sorted inside one workgroup), got %d"
+                             % (MAX_QUANTILE_DRAWS, K))
+    return K, probs
+
+
+def draw_windows(K, n, d, budget=Z_WINDOW_BYTES):
+    """[(k_lo, k_cnt)] covering K draws so that a window's z buffer [k_cnt, n, d] float32 stays within `budget`
+    (one draw per window when even a single draw exceeds it)"""
+    per = max(1, int(n) * int(d) * 4)
+    cnt = max(1, min(int(K), budget // per))
+    return [(lo, min(cnt, K - lo)) for lo in range(0, int(K), cnt)]
+
+
+def quantile_row_chunks(n, d, K, budget=XT_CHUNK_BYTES):
+    """[(lo, m)] covering n rows so that a chunk's transposed draws [m, d, K] float32 stay within `budget` (one row per
+    chunk when even a single row exceeds it); one chunk when everything fits"""
+    n = int(n)
+    if n == 0:
+        return []
+    per = max(1, int(d) * int(K) * 4)
+    rows = max(1, min(n, budget // per))
+    return [(lo, min(rows, n - lo)) for lo in range(0, n, rows)]
+
+
+def route(nf, supported=None):
+    """'kernel' or the reason the call runs as the notebook's loop on the host: 'layerwise' (layers that cannot run as one
+    fused stack), 'prior' (a prior object the user assigned), 'shape' (the kernels do not hold the shape in LDS).
+    `supported`: callable () -> bool asked last (it needs the engine); None skips that question."""
+    from .nflow import StandardNormalPrior
+    if nf._layerwise():
+        return "layerwise"
+    if not isinstance(nf.prior, StandardNormalPrior):
+        return "prior"
+    if supported is not None and not supported():
+        return "shape"
+    return "kernel"
+
+
+def stats_of_draws(X, probs, ddof):
+    """the notebook's numpy reductions over stacked draws X [K, n, d], in float64, rounded once to float32"""
+    X64 = np.asarray(X, dtype=np.float64)
+    K = X64.shape[0]
+    f = lambda a: np.asarray(a, dtype=np.float32)
+    with np.errstate(all="ignore"):
+        std = X64.std(axis=0, ddof=ddof) if K > ddof else np.full(X64.shape[1:], np.nan)
+        q = None if probs is None else f(np.quantile(X64, list(probs), axis=0).reshape((len(probs),) + X64.shape[1:]))
+        return SampleStats(f(X64.mean(axis=0)), f(std), f(X64.min(axis=0)), f(X64.max(axis=0)), q)
+
+
+def _conditions(nf, C, eng):
+    if type(C) == type(1):            # python int only, as nflow.py:135
+        return C, None
+    return len(C), nf._on_device(C, eng)
+
+
+def _host_draws(n, d, dev):
+    """how the host prior makes one draw of randn(n, d): 'device' (the generator's bits drawn on the device) or 'host'"""
+    from .nflow import HostStreamOnDevice
+    return "device" if (n * d >= 16 and HostStreamOnDevice.usable(dev)) else "host"
+
+
+def run(nf, C, K, probs, ddof, want_stats, want_draws):
+    """-> (SampleStats of device tensors or None, draws [K, n, d] device tensor or None).  The caller has checked route()."""
+    from . import _predict_lib as pl
+    from .nflow import HostStreamOnDevice
+    eng = nf.engine()
+    eng.sync_params()
+    n, Cd = _conditions(nf, C, eng)
+    Cd = eng._cond(Cd, n)
+    dev, d = eng.device, eng.d
+    host = nf.prior.host_rng
+    f32 = dict(dtype=torch.float32, device=dev)
+    x_out = torch.empty((K, n, d), **f32) if want_draws else None
+    state = pl.new_state(n, d, dev) if want_stats else None
+    q_out = torch.empty((len(probs), n, d), **f32) if (want_stats and probs is not None) else None
+    probs_dev = torch.tensor(probs, dtype=torch.float64, device=dev) if q_out is not None else None
+    chunks = quantile_row_chunks(n, d, K, XT_CHUNK_BYTES) if q_out is not None else ([(0, n)] if n else [])
+    keep = []
+
+    def rows_of(t, lo, m):
+        return None if t is None else t[lo:lo + m]
+
+    if not host:
+        seeds = [nf.prior.next_seed() for _ in range(K)]          # what K successive sample() calls consume
+        for lo, m in chunks:
+            xt = torch.empty((m, d, K), **f32) if q_out is not None else None
+            keep.append(eng.predict_draw(rows_of(Cd, lo, m), m, lo, seeds, None, n, 0, K, K, rows_of(state, lo, m), x_out, xt))
+            if xt is not None:
+                _chunk_quantiles(pl, xt, lo, m, d, K, probs_dev, q_out)
+        torch.cuda.current_stream(dev).synchronize()             # the host seed arrays have been consumed
+    elif n > 0:
+        how = _host_draws(n, d, dev)
+        windows = draw_windows(K, n, d, Z_WINDOW_BYTES)
+        start = torch.get_rng_state() if len(chunks) > 1 else None
+        zbuf = torch.empty((windows[0][1], n, d), **f32)
+        for ci, (lo, m) in enumerate(chunks):
+            if ci > 0:
+                torch.set_rng_state(start)                        # every row chunk walks the same K draws of randn(n, d)
+            xt = torch.empty((m, d, K), **f32) if q_out is not None else None
+            hs = HostStreamOnDevice(dev).begin() if how == "device" else None
+            try:
+                for k_lo, k_cnt in windows:
+                    zw = zbuf[:k_cnt]
+                    if hs is not None:
+                        if (n * d) % 16 == 0:
+                            hs.draw(zw)                           # whole 16-blocks: k_cnt draws of n d numbers are one draw
+                        else:
+                            for k in range(k_cnt):
+                                hs.draw(zw[k])
+                    else:
+                        zw.copy_(torch.stack([torch.randn((n, d)) for _ in range(k_cnt)]))
+                    eng.predict_draw(rows_of(Cd, lo, m), m, lo, None, zw, n, k_lo, k_cnt, K, rows_of(state, lo, m),
+                                     None if x_out is None else x_out[k_lo:k_lo + k_cnt], xt)
+            finally:
+                if hs is not None:
+                    hs.end()
+            if xt is not None:
+                _chunk_quantiles(pl, xt, lo, m, d, K, probs_dev, q_out)
+    stats = None
+    if want_stats:
+        mean, std, mn, mx = (torch.empty((n, d), **f32) for _ in range(4))
+        if n > 0:
+            pl.finalize(state, n, d, ddof, mean, std, mn, mx)
+        stats = SampleStats(mean, std, mn, mx, q_out)
+    del keep
+    return stats, x_out
+
+
+def _chunk_quantiles(pl, xt, lo, m, d, K, probs_dev, q_out):
+    """quantiles of one row chunk into rows lo .. lo + m of q_out [Q, n, d]"""
+    if m == q_out.shape[1]:
+        pl.quantiles(xt, m, d, K, probs_dev, q_out)
+        return
+    t = torch.empty((q_out.shape[0], m, d), dtype=torch.float32, device=q_out.device)
+    pl.quantiles(xt, m, d, K, probs_dev, t)
+    q_out[:, lo:lo + m].copy_(t)
+
+
+def loop_draws(sample, C, K):
+    """the notebook's loop: K successive sample(C) calls, stacked [K, n, d] (numpy float32)"""
+    return np.array([np.asarray(sample(C), dtype=np.float32) for _ in range(K)], dtype=np.float32)

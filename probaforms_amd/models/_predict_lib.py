@@ -1,0 +1,143 @@
+"""ctypes binding of libpf_predict.so (C ABI: probaforms_amd/models/predict_csrc/pf_predict.h).
+
+The library is built in-tree by `make -C probaforms_amd/models/predict_csrc` (see __graft_entry__.build) and loaded on the
+first call, so importing probaforms_amd.models needs no GPU.  A missing library or a tensor off the HIP device raises; a shape
+the kernels do not hold in LDS is reported by `supported()` / `Unsupported`, and the callers then run the loop the call
+replaces (see NormalizingFlow.sample_stats).
+"""
+import ctypes as C
+import os
+import threading
+
+import numpy as np
+import torch
+
+from .._hip import RnvpShape
+
+ABI_VERSION = 100                  # pfp_version() of the library this binding matches (pf_predict.h PFP_VERSION)
+EUNSUPPORTED = -2                  # PFP_EUNSUPPORTED
+STATE_BYTES = 32                   # PFP_STATE_BYTES
+MAX_QUANTILE_DRAWS = 8192          # PFP_MAX_QUANTILE_DRAWS
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "predict_csrc", "libpf_predict.so")
+
+_VP, _I64, _I32, _SZ, _SP = C.c_void_p, C.c_int64, C.c_int32, C.c_size_t, C.POINTER(RnvpShape)
+
+_SIGNATURES = {
+    "pfp_version": (C.c_int, []),
+    "pfp_status_string": (C.c_char_p, [C.c_int]),
+    "pfp_workspace_bytes": (_SZ, [_SP, _I64]),
+    "pfp_draw_accumulate": (C.c_int, [_VP, _SP, _VP, _VP, _VP, _I64, _I64, _VP, _VP, _I64, _I64, _I64, _I64, _VP, _VP, _VP,
+                                      _VP, _SZ]),
+    "pfp_finalize": (C.c_int, [_VP, _VP, _I64, _I32, _I32, _VP, _VP, _VP, _VP]),
+    "pfp_quantiles": (C.c_int, [_VP, _VP, _I64, _I32, _I64, _VP, _I32, _VP]),
+}
+EXPORTS = tuple(_SIGNATURES)
+
+_lib = None
+_lock = threading.Lock()
+
+
+class PredictLibraryMissing(RuntimeError):
+    pass
+
+
+class Unsupported(RuntimeError):
+    """the shape's per-tile image does not fit the LDS (PFP_EUNSUPPORTED)"""
+
+
+def lib():
+    """Load libpf_predict.so once; raise loudly if it has not been built or is another ABI version."""
+    global _lib
+    if _lib is None:
+        with _lock:
+            if _lib is None:
+                if not os.path.exists(LIB_PATH):
+                    raise PredictLibraryMissing(
+                        "%s not found: build it with `make -C probaforms_amd/models/predict_csrc` "
+                        "(or `python -c 'import __graft_entry__ as g; g.build()'`)." % LIB_PATH)
+                L = C.CDLL(LIB_PATH)
+                L.pfp_version.restype, L.pfp_version.argtypes = C.c_int, []
+                have = int(L.pfp_version())
+                if have != ABI_VERSION:
+                    raise PredictLibraryMissing("%s reports pfp_version() = %d, this binding is written for %d: rebuild it "
+                                                "(`make -C probaforms_amd/models/predict_csrc`)" % (LIB_PATH, have, ABI_VERSION))
+                for name, (res, args) in _SIGNATURES.items():
+                    fn = getattr(L, name)
+                    fn.restype, fn.argtypes = res, args
+                _lib = L
+    return _lib
+
+
+def check(status, what):
+    if status == EUNSUPPORTED:
+        raise Unsupported("%s: shape not supported" % what)
+    if status != 0:
+        msg = lib().pfp_status_string(status)
+        raise RuntimeError("%s failed: %s (status %d)" % (what, msg.decode() if msg else "?", status))
+
+
+def _ptr(t, dtype, what, nullable=False):
+    if t is None:
+        if nullable:
+            return None
+        raise RuntimeError("%s is required" % what)
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError("%s must be a tensor on a HIP device (got %s)" % (what, getattr(t, "device", type(t))))
+    if t.dtype != dtype or not t.is_contiguous():
+        raise RuntimeError("%s must be contiguous %s (got %s, contiguous=%s)" % (what, dtype, t.dtype, t.is_contiguous()))
+    return t.data_ptr()
+
+
+def _f32(t, what, nullable=False):
+    return _ptr(t, torch.float32, what, nullable)
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def workspace_bytes(shape, k_cnt):
+    """bytes of workspace for k_cnt draws per call; 0 = the kernels do not serve this shape"""
+    return int(lib().pfp_workspace_bytes(C.byref(shape), int(k_cnt)))
+
+
+def supported(shape):
+    return workspace_bytes(shape, 1) > 0
+
+
+def new_state(n_rows, d, device):
+    """zeroed running moments [n_rows, d] (PFP_STATE_BYTES each): nothing seen yet"""
+    return torch.zeros((int(n_rows), int(d), STATE_BYTES), dtype=torch.uint8, device=device)
+
+
+def draw_accumulate(shape, params, masks, c, n_rows, row_offset, seeds, z, n_total, k_lo, k_cnt, k_total, state, x_out, xt_out,
+                    ws):
+    """seeds: sequence of k_cnt ints (host) or None; z: device tensor [k_cnt, n_total, d] or None.  Returns the host seed
+    array, which the caller keeps alive until the stream has consumed it."""
+    hseeds = None
+    if seeds is not None:
+        hseeds = np.ascontiguousarray(np.asarray([int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds], dtype=np.uint64))
+        if hseeds.size != int(k_cnt):
+            raise ValueError("seeds must hold k_cnt = %d entries, got %d" % (k_cnt, hseeds.size))
+    check(lib().pfp_draw_accumulate(_stream(), C.byref(shape), _f32(params, "params"), _ptr(masks, torch.uint8, "masks", True),
+                                    _f32(c, "C", True), int(n_rows), int(row_offset),
+                                    None if hseeds is None else hseeds.ctypes.data, _f32(z, "z", True), int(n_total),
+                                    int(k_lo), int(k_cnt), int(k_total), _ptr(state, torch.uint8, "state", True),
+                                    _f32(x_out, "x_out", True), _f32(xt_out, "xt_out", True),
+                                    _ptr(ws, torch.uint8, "workspace", True), 0 if ws is None else ws.numel()),
+          "pfp_draw_accumulate")
+    return hseeds
+
+
+def finalize(state, n_rows, d, ddof, mean, std, mn, mx):
+    check(lib().pfp_finalize(_stream(), _ptr(state, torch.uint8, "state"), int(n_rows), int(d), int(ddof),
+                             _f32(mean, "mean", True), _f32(std, "std", True), _f32(mn, "min", True), _f32(mx, "max", True)),
+          "pfp_finalize")
+
+
+def quantiles(xt, n_rows, d, k_total, probs, q_out):
+    """probs: float64 device tensor [Q]; q_out: float32 [Q, n_rows, d]"""
+    check(lib().pfp_quantiles(_stream(), _f32(xt, "xt"), int(n_rows), int(d), int(k_total),
+                              _ptr(probs, torch.float64, "probs"), int(probs.numel()), _f32(q_out, "q_out")), "pfp_quantiles")

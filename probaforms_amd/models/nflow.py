@@ -336,6 +336,40 @@ class NormalizingFlow(nn.Module):
             return eng.inverse_autograd(z, C)
         return eng.inverse(z, C, out=z)
 
+    # -- multi-draw predictive statistics (names the reference does not have; models/_predict.py) -----------------
+    def _predict_route(self):
+        from . import _predict
+        return _predict.route(self, lambda: self.engine().predict_supported())
+
+    def sample_many(self, C, n_draws):
+        """``torch.stack([self.sample(C) for _ in range(n_draws)])`` -> [n_draws, n, var_size] on the device, in one
+        launch per window of draws (pfp_draw_accumulate) instead of one per draw.  Consumes torch's global CPU generator
+        exactly as the n_draws successive ``sample(C)`` calls do; no autograd graph is recorded.  A layer-wise flow, a
+        user-assigned prior and a shape the kernel does not hold in LDS run that loop itself."""
+        from . import _predict
+        K, _ = _predict.validate(n_draws)
+        with torch.no_grad():
+            if self._predict_route() != "kernel":
+                return torch.stack([torch.as_tensor(self.sample(C), dtype=torch.float32) for _ in range(K)])
+            return _predict.run(self, C, K, None, 0, False, True)[1]
+
+    def sample_stats(self, C, n_draws=100, quantiles=None, ddof=0):
+        """Per condition row, the statistics over ``n_draws`` samples that the reference's notebooks take from a Python loop
+        of ``sample(C)`` calls: ``SampleStats(mean, std, min, max, quantiles)`` of float32 device tensors [n, var_size]
+        (quantiles: [Q, n, var_size], numpy's default 'linear' method, or None).  The draws are pushed through the inverse
+        flow and reduced on the device (float64 sums, one rounding); they are never stored unless quantiles are asked
+        for.  Consumes torch's global CPU generator exactly as the loop does.  ``n_draws < 1``, a probability outside
+        [0, 1] or quantiles with ``n_draws > 8192`` raise ValueError.  A layer-wise flow, a user-assigned prior and a shape
+        the kernel does not hold in LDS fall back to that loop on the host (``sample`` n_draws times plus numpy)."""
+        from . import _predict
+        K, probs = _predict.validate(n_draws, quantiles, ddof)
+        with torch.no_grad():
+            if self._predict_route() != "kernel":
+                X = _predict.loop_draws(lambda c: torch.as_tensor(self.sample(c)).detach().cpu().numpy(), C, K)
+                s = _predict.stats_of_draws(X, probs, ddof)
+                return _predict.SampleStats(*(None if a is None else torch.from_numpy(a).to(DEVICE) for a in s))
+            return _predict.run(self, C, K, probs, int(ddof), True, False)[0]
+
     # -- host staging (SURVEY.md 8(f) rank 3) -------------------------------------------------
     # one chunk of output rows: at least PIPELINE_CHUNK_BYTES and at least PIPELINE_MIN_ROWS rows (a launch of fewer
     # rows leaves CUs idle: 256 rows per workgroup).  Measured at API level, C2 sample(1M): 8 MB chunks 3.1 ms (device

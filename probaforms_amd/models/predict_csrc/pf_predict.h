@@ -1,0 +1,106 @@
+/*
+ * pf_predict.h -- C ABI of libpf_predict.so: multi-draw predictive statistics of a conditional RealNVP flow on
+ * the MI355X (gfx950).  For every condition row it pushes K prior draws through the inverse flow
+ * (RealNVPLayer.g, realnvp.py:104-129; NormalizingFlow.sample, nflow.py:142-143) and reduces across the draws
+ * on the device: what the reference's notebooks do with a Python loop of `model.sample(X)` calls followed by
+ * numpy's mean / std / quantile over the stacked results.
+ *
+ *   pfp_draw_accumulate   K draws per row through the inverse flow; running moments, the draws, their transpose
+ *   pfp_finalize          running moments -> mean, std, min, max
+ *   pfp_quantiles         exact quantiles (numpy's default 'linear') of the transposed draws
+ *
+ * Conventions (as pf_cnormal.h)
+ *   - every array is a DEVICE pointer unless it says HOST; sizes are plain integers;
+ *   - the caller owns all device memory including the workspace (no hidden hipMalloc);
+ *   - kernels are enqueued on `stream` (a hipStream_t passed as void*) and the call returns without synchronising;
+ *   - return value: 0 ok; <0 argument error (PFP_E*); >0 a hipError_t;
+ *   - no global mutable state other than the one-time kernel attribute setup; no float atomics: the same inputs
+ *     give bitwise the same outputs.
+ *
+ * Data layout: `shape`, `params` and `masks` are those of include/rnvp_hip.h (flat float32 parameters in
+ * nf.parameters() order; masks [L, d] uint8, 1 = pass-through; masks may be NULL when shape->alt_masks is 1 or 2).
+ * Of rnvp_shape only L, d, c, n_hidden, hidden, act and alt_masks are read.
+ *
+ * Rows and draws.  A call handles the condition rows row_offset .. row_offset + n_rows of a larger job and the
+ * draws k_lo .. k_lo + k_cnt of K_total.  Row r's results depend only on (seeds / z, the GLOBAL row, c[r]): any
+ * split of the rows over calls gives bitwise the result of one call.  A split of the draws into windows changes
+ * the order of the float64 sums, so windows agree to rounding only.
+ */
+#ifndef PF_PREDICT_H
+#define PF_PREDICT_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../../include/rnvp_hip.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define PFP_OK            0
+#define PFP_EINVAL       (-1)   /* NULL pointer, negative size, bad shape                                    */
+#define PFP_EUNSUPPORTED (-2)   /* one draw tile's image does not fit the LDS, or K_total > PFP_MAX_QUANTILE_DRAWS */
+#define PFP_EWORKSPACE   (-3)   /* workspace smaller than pfp_workspace_bytes() says                         */
+
+#define PFP_VERSION 100         /* pfp_version(): bumped whenever an argument list or the state layout changes */
+
+#define PFP_MAX_QUANTILE_DRAWS 8192   /* pfp_quantiles sorts one (row, column) series inside one workgroup's LDS */
+
+/*
+ * Running moments of one (row, column): PFP_STATE_BYTES bytes, all zero = nothing seen yet.
+ *   float64 sum, sumsq   of (x - shift) and its square over the draws seen
+ *   float32 shift        the first draw seen
+ *   float32 min, max
+ *   uint32  count
+ * The values accumulated are the float32 values x_out receives.
+ */
+#define PFP_STATE_BYTES 32
+
+int         pfp_version(void);
+const char *pfp_status_string(int status);
+
+/* bytes of device workspace pfp_draw_accumulate needs for k_cnt draws per call; 0 for an invalid or unsupported shape */
+size_t pfp_workspace_bytes(const rnvp_shape *shape, int64_t k_cnt);
+
+/*
+ * x[k][r] = g(z[k][r], c[r]) for the n_rows rows and k_cnt draws of this call, in ONE launch.
+ *   c       [n_rows, cdim]            conditions of this call's rows (NULL iff cdim == 0)
+ *   seeds   HOST [k_cnt] uint64       draw k_lo + i uses z[r][j] = the counter-based prior value of
+ *                                     (seeds[i], row_offset + r, j): the numbers rnvp_sample(seed = seeds[i],
+ *                                     row_offset) uses, drawn in registers and never written; or NULL and
+ *   z       [k_cnt, n_total, d]       the prior draws themselves, indexed by GLOBAL row (row_offset + r < n_total)
+ *   state   [n_rows, d] x PFP_STATE_BYTES   (nullable) read, updated with this call's draws, written back
+ *   x_out   [k_cnt, n_rows, d]        (nullable) the draws
+ *   xt_out  [n_rows, d, k_total]      (nullable) the draws transposed, written at columns k_lo .. k_lo + k_cnt
+ * Exactly one of seeds / z is given.  On either path row_offset + n_rows <= n_total (the rows of the whole job) and
+ * k_lo + k_cnt <= k_total, whichever outputs are asked for (PFP_EINVAL otherwise).  PFP_EUNSUPPORTED when the shape's per-tile image exceeds a CU's LDS.
+ */
+int pfp_draw_accumulate(void *stream, const rnvp_shape *shape, const float *params, const uint8_t *masks,
+                        const float *c, int64_t n_rows, int64_t row_offset,
+                        const uint64_t *seeds, const float *z, int64_t n_total,
+                        int64_t k_lo, int64_t k_cnt, int64_t k_total,
+                        void *state, float *x_out, float *xt_out,
+                        void *workspace, size_t workspace_bytes);
+
+/*
+ * state -> mean, std (divisor count - ddof), min, max, each [n_rows, d] float32 and nullable.  float64 arithmetic,
+ * one rounding to float32 at the end.  A series with count <= ddof gives std = NaN, as numpy does; count == 0
+ * gives NaN everywhere.
+ */
+int pfp_finalize(void *stream, const void *state, int64_t n_rows, int32_t d, int32_t ddof,
+                 float *mean, float *std, float *min, float *max);
+
+/*
+ * q_out[i][r][j] = numpy.quantile(xt[r][j][:], probs[i]) (method 'linear'), evaluated in float64 on the sorted
+ * series and rounded once.  xt [n_rows, d, k_total] (pfp_draw_accumulate's xt_out; not modified),
+ * probs [n_probs] float64 in [0, 1], 1 <= k_total <= PFP_MAX_QUANTILE_DRAWS.  Any k_total: the sort pads to a
+ * power of two with keys above every float, which are never selected.
+ */
+int pfp_quantiles(void *stream, const float *xt, int64_t n_rows, int32_t d, int64_t k_total,
+                  const double *probs, int32_t n_probs, float *q_out);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -277,6 +277,39 @@ class RealNVP(GenModel):
             X = self.nf.sample(C).cpu().detach().numpy()
         return X
 
+    def sample_many(self, C=100, n_draws=100):
+        """``np.array([self.sample(C) for _ in range(n_draws)])`` -> float32 numpy [n_draws, n, d] (a name the reference does not have):
+        the draws of the notebooks' predictive loop in one launch per window of draws.  Consumes torch's global CPU
+        generator exactly as the loop does.  A layer-wise flow, a user-assigned prior and a shape the kernel does not hold
+        in LDS run the loop itself."""
+        from . import _predict
+        K, _ = _predict.validate(n_draws)
+        if self.nf._predict_route() != "kernel":
+            return _predict.loop_draws(self.sample, C, K)
+        if type(C) != type(1):
+            C = _to_device_f32(C, self.nf.engine().device)
+        return self.nf.sample_many(C, K).cpu().numpy()
+
+    def sample_stats(self, C=100, n_draws=100, quantiles=None, ddof=0):
+        """Predictive statistics per condition row over ``n_draws`` samples (a name the reference does not have): what
+        docs/examples/regression.ipynb and forecast.ipynb compute from a Python loop of ``sample(C)`` calls with
+        ``.mean(axis=0)``, ``.std(axis=0)`` and ``np.quantile(..., axis=0)``.  Returns ``SampleStats(mean, std, min, max,
+        quantiles)``: float32 numpy arrays [n, d]; quantiles [Q, n, d] (numpy's 'linear' method) or None.  ``C`` is an array
+        or a python int, as in ``sample``.  The draws are made, pushed through the flow and reduced on the device; only the
+        statistics come back.  Consumes torch's global CPU generator exactly as the loop does (host prior: n_draws draws of
+        randn(n, d); prior_rng='device': n_draws seeds), so a seeded call reproduces the seeded loop to rounding and leaves
+        the generator where the loop leaves it.  ``n_draws < 1``, a probability outside [0, 1] or quantiles with
+        ``n_draws > 8192`` raise ValueError.  A layer-wise flow, a user-assigned prior and a shape the kernel does not hold
+        in LDS fall back to the loop on the host (``self.sample`` n_draws times plus numpy), so the call always works."""
+        from . import _predict
+        K, probs = _predict.validate(n_draws, quantiles, ddof)
+        if self.nf._predict_route() != "kernel":
+            return _predict.stats_of_draws(_predict.loop_draws(self.sample, C, K), probs, int(ddof))
+        if type(C) != type(1):
+            C = _to_device_f32(C, self.nf.engine().device)
+        s = self.nf.sample_stats(C, K, probs, int(ddof))
+        return _predict.SampleStats(*(None if a is None else a.cpu().numpy() for a in s))
+
     def _sample_sharded(self, C, n, rank, world, gather):
         import torch.distributed as dist
         eng = self.nf.engine()
