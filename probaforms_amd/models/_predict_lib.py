@@ -14,7 +14,7 @@ import torch
 
 from .._hip import RnvpShape
 
-ABI_VERSION = 100                  # pfp_version() of the library this binding matches (pf_predict.h PFP_VERSION)
+ABI_VERSION = 101                  # pfp_version() of the library this binding matches (pf_predict.h PFP_VERSION)
 EUNSUPPORTED = -2                  # PFP_EUNSUPPORTED
 STATE_BYTES = 32                   # PFP_STATE_BYTES
 MAX_QUANTILE_DRAWS = 8192          # PFP_MAX_QUANTILE_DRAWS

@@ -43,17 +43,22 @@ extern "C" {
 #define PFP_EUNSUPPORTED (-2)   /* one draw tile's image does not fit the LDS, or K_total > PFP_MAX_QUANTILE_DRAWS */
 #define PFP_EWORKSPACE   (-3)   /* workspace smaller than pfp_workspace_bytes() says                         */
 
-#define PFP_VERSION 100         /* pfp_version(): bumped whenever an argument list or the state layout changes */
+#define PFP_VERSION 101         /* pfp_version(): bumped whenever an argument list or the state's layout or meaning changes */
 
 #define PFP_MAX_QUANTILE_DRAWS 8192   /* pfp_quantiles sorts one (row, column) series inside one workgroup's LDS */
 
 /*
  * Running moments of one (row, column): PFP_STATE_BYTES bytes, all zero = nothing seen yet.
  *   float64 sum, sumsq   of (x - shift) and its square over the draws seen
- *   float32 shift        the first draw seen
- *   float32 min, max
+ *   float32 shift        the first draw seen, or 0 when that draw is not finite (inf - shift then stays inf)
+ *   float32 min, max     NaN once a NaN has been seen (numpy's min / max, not fminf / fmaxf)
  *   uint32  count
  * The values accumulated are the float32 values x_out receives.
+ *
+ * Non-finite draws follow numpy over the stacked draws.  A series holding a NaN: mean, std, min, max and every quantile
+ * are NaN.  A series holding +inf (or -inf) and no NaN: mean +inf (-inf), std NaN, min / max exact; both infinities:
+ * mean NaN.  A quantile that interpolates from or to an infinity is what numpy's lerp gives (NaN where it forms
+ * inf * 0 or inf - inf).  Each (row, column) series is reduced on its own: a NaN never leaves its series.
  */
 #define PFP_STATE_BYTES 32
 
@@ -86,7 +91,7 @@ int pfp_draw_accumulate(void *stream, const rnvp_shape *shape, const float *para
 /*
  * state -> mean, std (divisor count - ddof), min, max, each [n_rows, d] float32 and nullable.  float64 arithmetic,
  * one rounding to float32 at the end.  A series with count <= ddof gives std = NaN, as numpy does; count == 0
- * gives NaN everywhere.
+ * gives NaN everywhere.  Non-finite draws: see the state comment above.
  */
 int pfp_finalize(void *stream, const void *state, int64_t n_rows, int32_t d, int32_t ddof,
                  float *mean, float *std, float *min, float *max);
@@ -95,7 +100,8 @@ int pfp_finalize(void *stream, const void *state, int64_t n_rows, int32_t d, int
  * q_out[i][r][j] = numpy.quantile(xt[r][j][:], probs[i]) (method 'linear'), evaluated in float64 on the sorted
  * series and rounded once.  xt [n_rows, d, k_total] (pfp_draw_accumulate's xt_out; not modified),
  * probs [n_probs] float64 in [0, 1], 1 <= k_total <= PFP_MAX_QUANTILE_DRAWS.  Any k_total: the sort pads to a
- * power of two with keys above every float, which are never selected.
+ * power of two with keys above every float, which are never selected.  A series holding a NaN of either sign gives
+ * NaN for every probability.
  */
 int pfp_quantiles(void *stream, const float *xt, int64_t n_rows, int32_t d, int64_t k_total,
                   const double *probs, int32_t n_probs, float *q_out);

@@ -70,6 +70,10 @@ Geo make_geo(const KShape &s, int RS) {
 
 __device__ __forceinline__ f4 mfma16(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
+// numpy's min / max: NaN when either operand is NaN (fminf / fmaxf return the other operand)
+__device__ __forceinline__ float min_nan(float a, float b) { return (a != a || b != b) ? NAN : fminf(a, b); }
+__device__ __forceinline__ float max_nan(float a, float b) { return (a != a || b != b) ? NAN : fmaxf(a, b); }
+
 __device__ __forceinline__ float mask_of(const KShape &s, const uint8_t *__restrict__ masks, int l, int j) {
     if (masks) return (float)masks[l * s.d + j];
     return (float)((j + l + (s.alt == 2 ? 1 : 0)) & 1);
@@ -238,7 +242,7 @@ k_draw(KShape s, Geo g, const float *__restrict__ params, const uint8_t *__restr
                         const bool ok = jok && col < ncols;
                         const float v = X[(jok ? j : 0) * RS + col];
                         const float first = __shfl(v, lane & 48);
-                        if (st.count == 0) st.shift = first;
+                        if (st.count == 0) st.shift = isfinite(first) ? first : 0.f;
                         const double dv = ok ? (double)v - (double)st.shift : 0.0;
                         double s1 = dv, s2 = dv * dv;
                         float mn = ok ? v : INFINITY, mx = ok ? v : -INFINITY;
@@ -246,13 +250,13 @@ k_draw(KShape s, Geo g, const float *__restrict__ params, const uint8_t *__restr
                         for (int w = 8; w >= 1; w >>= 1) {
                             s1 += __shfl_xor(s1, w);
                             s2 += __shfl_xor(s2, w);
-                            mn = fminf(mn, __shfl_xor(mn, w));
-                            mx = fmaxf(mx, __shfl_xor(mx, w));
+                            mn = min_nan(mn, __shfl_xor(mn, w));
+                            mx = max_nan(mx, __shfl_xor(mx, w));
                         }
                         const int nv = ncols - 16 * t;
                         if (nv > 0) {
                             st.sum += s1; st.sumsq += s2;
-                            st.mn = fminf(st.mn, mn); st.mx = fmaxf(st.mx, mx);
+                            st.mn = min_nan(st.mn, mn); st.mx = max_nan(st.mx, mx);
                             st.count += (uint32_t)(nv < 16 ? nv : 16);
                         }
                     }
@@ -297,7 +301,9 @@ __device__ __forceinline__ float val_of(uint32_t k) {
 }
 
 // one workgroup per (row, column) series: bitonic sort of P = 2^ceil(log2 K) keys in LDS, the P - K pad keys are
-// 0xffffffff (at or above every float's key) and only indices below K are read afterwards
+// 0xffffffff (at or above every float's key) and only indices below K are read afterwards.  NaNs sort to the two ends
+// (by sign), so a series holds one iff keys[0] or keys[K - 1] decodes to NaN: every quantile of it is then NaN, as
+// numpy.quantile gives
 __global__ void __launch_bounds__(256)
 k_quantiles(const float *__restrict__ xt, int64_t n_series, int K, int P, const double *__restrict__ probs, int nq,
             float *__restrict__ q_out) {
@@ -319,6 +325,8 @@ k_quantiles(const float *__restrict__ xt, int64_t n_series, int K, int P, const 
                 __syncthreads();
             }
         }
+        const float v_lo = val_of(keys[0]), v_hi = val_of(keys[K - 1]);
+        const bool has_nan = v_lo != v_lo || v_hi != v_hi;
         for (int i = tid; i < nq; i += 256) {
             // numpy's 'linear': virtual index p (K - 1), then _lerp(a, b, t)
             const double pos = probs[i] * (double)(K - 1);
@@ -332,6 +340,7 @@ k_quantiles(const float *__restrict__ xt, int64_t n_series, int K, int P, const 
             double res = a + diff * t;
             if (t >= 0.5) res = b - diff * (1.0 - t);
             if (diff == 0.0) res = a;
+            if (has_nan) res = NAN;
             q_out[(int64_t)i * n_series + sr] = (float)res;
         }
         __syncthreads();

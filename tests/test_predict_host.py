@@ -26,7 +26,7 @@ def test_exports_and_version_match_the_header_text():
         params = [p for p in m.group(1).split(",") if p.strip() and p.strip() != "void"]
         assert len(params) == len(args), name
     consts = dict(re.findall(r"#define\s+(PFP_[A-Z_]+)\s+\(?(-?\d+)\)?", _header()))
-    assert int(consts["PFP_VERSION"]) == pl.ABI_VERSION == 100
+    assert int(consts["PFP_VERSION"]) == pl.ABI_VERSION == 101
     assert int(consts["PFP_STATE_BYTES"]) == pl.STATE_BYTES
     assert int(consts["PFP_MAX_QUANTILE_DRAWS"]) == pl.MAX_QUANTILE_DRAWS
     assert int(consts["PFP_EUNSUPPORTED"]) == pl.EUNSUPPORTED
@@ -167,3 +167,117 @@ def test_draw_accumulate_checks_rows_and_draws_before_any_launch():
     assert call(5, 3, 8, 2, 4, 5) == -1           # draws 2 .. 6 of 5
     assert call(5, 3, 8, 0, 0, 4) == -1
     assert call(-1, 0, 8, 0, 4, 4) == -1
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The comparison rules of tests/test_predict_edges_gpu.py can fail: numpy stand-ins for wrong kernels are rejected by them on
+# the series that file feeds the kernels, and the host route (stats_of_draws) passes.
+# ---------------------------------------------------------------------------------------------------------------------------
+def _standin_moments(x, windows, ddof, shift, nan_minmax):
+    """pf_predict.hip's k_draw / k_finalize arithmetic over x [K, ...] in numpy: float64 sums of (x - shift) and its square,
+    16-draw tile by tile.  shift: 'first' (the first draw, whatever it is), 'finite' (0 when that draw is not finite) or
+    'none' (plain sums).  nan_minmax: numpy's min / max, else fmin / fmax (which drop NaN)."""
+    x = np.asarray(x, np.float32)
+    x64 = x.astype(np.float64)
+    with np.errstate(all="ignore"):
+        sh = {"first": x64[0], "finite": np.where(np.isfinite(x64[0]), x64[0], 0.0), "none": np.zeros_like(x64[0])}[shift]
+        s, ss, cnt = np.zeros_like(sh), np.zeros_like(sh), 0
+        for lo, hi in windows:
+            for t0 in range(lo, hi, 16):
+                dv = x64[t0:min(hi, t0 + 16)] - sh
+                s, ss, cnt = s + dv.sum(0), ss + (dv * dv).sum(0), cnt + len(dv)
+        q = ss - s * s / cnt
+        q = np.where(q < 0.0, 0.0, q)
+        std = np.sqrt(q / (cnt - ddof)) if cnt > ddof else np.full_like(q, np.nan)
+        if nan_minmax:
+            mn, mx = x.min(0), x.max(0)
+        else:                                             # folded into a state that starts at +inf / -inf
+            mn, mx = np.fmin(np.float32(np.inf), np.fmin.reduce(x, axis=0)), np.fmax(np.float32(-np.inf), np.fmax.reduce(x, axis=0))
+        return [a.astype(np.float32) for a in (sh + s / cnt, std, mn, mx)]
+
+
+def _standin_quantiles(xt, probs, nan_check):
+    """k_quantiles in numpy: sort by the kernel's uint32 key (negative NaNs first, positive NaNs last), numpy's lerp in float64"""
+    xt = np.asarray(xt, np.float32)
+    K = xt.shape[-1]
+    b = xt.view(np.uint32)
+    keys = np.where(b & 0x80000000, ~b, b | 0x80000000).astype(np.uint32)
+    srt = np.take_along_axis(xt, np.argsort(keys, axis=-1, kind="stable"), axis=-1).astype(np.float64)
+    out = np.empty((len(probs),) + xt.shape[:-1], np.float32)
+    with np.errstate(all="ignore"):
+        for i, p in enumerate(probs):
+            pos = p * (K - 1)
+            fl = min(max(np.floor(pos), 0.0), K - 1.0)
+            lo, t = int(fl), pos - fl
+            a, bb = srt[..., lo], srt[..., min(lo + 1, K - 1)]
+            diff = bb - a
+            res = bb - diff * (1.0 - t) if t >= 0.5 else a + diff * t
+            res = np.where(diff == 0.0, a, res)
+            if nan_check:
+                res = np.where(np.isnan(srt[..., 0]) | np.isnan(srt[..., K - 1]), np.nan, res)
+            out[i] = res
+    return out
+
+
+def _rejected(check, *args):
+    try:
+        check(*args)
+    except AssertionError:
+        return True
+    return False
+
+
+@pytest.mark.parametrize("K", [19, 40])
+def test_edge_rules_reject_fmin_fmax_and_a_non_finite_shift(K):
+    import predict_edge_series as E
+    from probaforms_amd.models import _predict as P
+    x = E.nonfinite(K)
+    for ddof in (0, 1):
+        for w in E.windows_of(K):
+            today = _standin_moments(x, w, ddof, "first", False)
+            fixed = _standin_moments(x, w, ddof, "finite", True)
+            E.check_moments(fixed, x, ddof, "fixed")
+            assert _rejected(E.check_moments, today, x, ddof, "today")
+            for j, kind in enumerate(E.NONFINITE_KINDS):
+                bad = _rejected(E.check_moments, [a[:, j] for a in today], x[:, :, j], ddof, kind)
+                # fmin / fmax lose every NaN; an infinite first draw turns the shifted sums into NaN; an infinity met later,
+                # and the two zeros, are right either way
+                assert bad == (j <= 6), (kind, bad)
+            np.testing.assert_array_equal(fixed[0][:, 9], np.zeros(3, np.float32))
+        s = P.stats_of_draws(x, None, ddof)
+        E.check_moments([s.mean, s.std, s.min, s.max], x, ddof, "stats_of_draws")
+
+
+@pytest.mark.parametrize("K", [3, 4, 5, 17, 4097, 8191])
+def test_edge_rules_reject_quantiles_that_overlook_a_nan(K):
+    import predict_edge_series as E
+    from probaforms_amd.models import _predict as P
+    xt, probs = E.quantile_series(K)
+    want = E.quantile_reference(xt, probs)
+    assert np.isnan(want[:, 0, 1]).all() and np.isnan(want[:, 1, 0]).all()      # a NaN of either sign: every quantile
+    E.same(_standin_quantiles(xt, probs, True), want, "fixed")
+    today = _standin_quantiles(xt, probs, False)
+    for r in range(3):
+        for j in range(2):
+            kind = E.QUANTILE_KINDS[2 * r + j]
+            assert _rejected(E.same, today[:, r, j], want[:, r, j], kind) == (kind in ("+nan", "-nan")), kind
+    s = P.stats_of_draws(np.moveaxis(xt, -1, 0), probs, 0)
+    E.same(s.quantiles, want, "stats_of_draws")
+
+
+@pytest.mark.parametrize("K", [1, 2, 15, 16, 17, 19, 40, 65, 1000])
+def test_edge_rules_reject_unshifted_sums(K):
+    import predict_edge_series as E
+    from probaforms_amd.models import _predict as P
+    x = E.conditioned(K)
+    assert np.isfinite(x).all() and (np.abs(x) > 1e-30).all()
+    for ddof in (0, 1):
+        for w in E.windows_of(K):
+            E.check_moments(_standin_moments(x, w, ddof, "finite", True), x, ddof, "shifted")
+            plain = _standin_moments(x, w, ddof, "none", True)
+            # the float64 sums of x and x^2 lose the variance of a series whose mean is 10^6 .. 10^7 standard deviations; with
+            # few draws, or the two-valued series at an even count, those sums can still come out exact
+            for j in ((0, 1, 4) if K in (19, 65, 1000) else ((0,) if K >= 15 else ())):
+                assert _rejected(E.check_moments, [a[:, j] for a in plain], x[:, :, j], ddof, E.CONDITIONED_KINDS[j])
+        s = P.stats_of_draws(x, None, ddof)
+        E.check_moments([s.mean, s.std, s.min, s.max], x, ddof, "stats_of_draws")
