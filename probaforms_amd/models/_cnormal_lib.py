@@ -10,7 +10,7 @@ import threading
 
 import torch
 
-ABI_VERSION = 100          # pfn_version() of the library this binding matches (pf_cnormal.h PFN_VERSION)
+ABI_VERSION = 101          # pfn_version() of the library this binding matches (pf_cnormal.h PFN_VERSION)
 MAX_HIDDEN = 8             # PFN_MAX_HIDDEN
 MAX_D = 32                 # PFN_MAX_D
 ACT_TANH, ACT_RELU, ACT_SIGMOID = 0, 1, 2  # PFN_ACT_*
@@ -46,6 +46,13 @@ class Adam(C.Structure):
                 ("weight_decay", C.c_double)]
 
 
+class TilingInfo(C.Structure):
+    """pfn_tiling_info"""
+    _fields_ = [("step_tile", C.c_int32), ("step_cap", C.c_int32), ("fwd_tile", C.c_int32), ("reserved", C.c_int32),
+                ("step_wgs", C.c_int64), ("step_wg_bound", C.c_int64), ("step_lds_bytes", C.c_int64),
+                ("fwd_lds_bytes", C.c_int64)]
+
+
 _VP, _I64, _SZ, _SP, _OP = C.c_void_p, C.c_int64, C.c_size_t, C.POINTER(Shape), C.POINTER(Adam)
 
 _SIGNATURES = {
@@ -53,6 +60,7 @@ _SIGNATURES = {
     "pfn_status_string": (C.c_char_p, [C.c_int]),
     "pfn_param_count": (_I64, [_SP]),
     "pfn_workspace_bytes": (_SZ, [_SP, _I64]),
+    "pfn_tiling": (C.c_int, [_SP, _I64, C.POINTER(TilingInfo)]),
     "pfn_forward": (C.c_int, [_VP, _SP, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _VP]),
     "pfn_loss_grad": (C.c_int, [_VP, _SP, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _VP, _SZ]),
     "pfn_train_step": (C.c_int, [_VP, _SP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _OP, _I64, _VP, _VP, _VP, _VP, _SZ]),
@@ -127,6 +135,16 @@ def param_count(shape):
 
 def workspace_bytes(shape, batch_rows):
     return int(lib().pfn_workspace_bytes(C.byref(shape), int(batch_rows)))
+
+
+def tiling(shape, rows, require_step=True):
+    """pfn_tiling_info of a training step / a forward call on `rows` rows (host only: no GPU needed).  A shape whose step
+    cannot run raises, as every other call does, unless require_step is False: the step fields are then 0"""
+    info = TilingInfo()
+    st = lib().pfn_tiling(C.byref(shape), int(rows), C.byref(info))
+    if st != EUNSUPPORTED or require_step:
+        check(st, "pfn_tiling")
+    return info
 
 
 def adam(lr, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8):

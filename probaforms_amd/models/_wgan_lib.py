@@ -10,7 +10,7 @@ import threading
 
 import torch
 
-ABI_VERSION = 100          # pfw_version() of the library this binding matches (pf_wgan.h PFW_VERSION)
+ABI_VERSION = 101          # pfw_version() of the library this binding matches (pf_wgan.h PFW_VERSION)
 MAX_HIDDEN = 8             # PFW_MAX_HIDDEN
 ACT_TANH, ACT_RELU = 0, 1  # PFW_ACT_*
 NET_G, NET_D = 0, 1        # PFW_NET_*
@@ -51,6 +51,14 @@ class RMSprop(C.Structure):
                 ("clamp", C.c_double)]
 
 
+class TilingInfo(C.Structure):
+    """pfw_tiling_info"""
+    _fields_ = [("step_tile", C.c_int32), ("step_cap", C.c_int32), ("eloss_tile", C.c_int32), ("gen_tile", C.c_int32),
+                ("crit_tile", C.c_int32), ("reserved", C.c_int32), ("step_wgs", C.c_int64), ("step_wg_bound", C.c_int64),
+                ("step_lds_bytes", C.c_int64), ("eloss_lds_bytes", C.c_int64), ("gen_lds_bytes", C.c_int64),
+                ("crit_lds_bytes", C.c_int64)]
+
+
 _VP, _I64, _SZ, _SP, _OP = C.c_void_p, C.c_int64, C.c_size_t, C.POINTER(Shape), C.POINTER(RMSprop)
 
 _SIGNATURES = {
@@ -58,6 +66,7 @@ _SIGNATURES = {
     "pfw_status_string": (C.c_char_p, [C.c_int]),
     "pfw_param_count": (_I64, [_SP, C.c_int]),
     "pfw_workspace_bytes": (_SZ, [_SP, _I64, _I64]),
+    "pfw_tiling": (C.c_int, [_SP, _I64, C.POINTER(TilingInfo)]),
     "pfw_generate": (C.c_int, [_VP, _SP, _VP, _VP, _VP, _I64, _VP]),
     "pfw_critic": (C.c_int, [_VP, _SP, _VP, _VP, _VP, _I64, _VP]),
     "pfw_loss_grad": (C.c_int, [_VP, _SP, C.c_int, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _SZ]),
@@ -134,6 +143,16 @@ def param_count(shape, net):
 
 def workspace_bytes(shape, batch_rows, loss_rows=0):
     return int(lib().pfw_workspace_bytes(C.byref(shape), int(batch_rows), int(loss_rows)))
+
+
+def tiling(shape, rows, require_step=True):
+    """pfw_tiling_info of a training step / an inference call on `rows` rows (host only: no GPU needed).  A shape whose step
+    cannot run raises, as every other call does, unless require_step is False: the step fields are then 0"""
+    info = TilingInfo()
+    st = lib().pfw_tiling(C.byref(shape), int(rows), C.byref(info))
+    if st != EUNSUPPORTED or require_step:
+        check(st, "pfw_tiling")
+    return info
 
 
 def rmsprop(lr, alpha=0.99, eps=1e-8, weight_decay=0.0, clamp=0.0):

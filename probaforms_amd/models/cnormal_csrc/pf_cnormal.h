@@ -52,7 +52,7 @@ extern "C" {
 #define PFN_EUNSUPPORTED (-2)   /* d > PFN_MAX_D, or one row's working set does not fit the LDS      */
 #define PFN_EWORKSPACE   (-3)   /* workspace smaller than pfn_workspace_bytes() says                 */
 
-#define PFN_VERSION 100         /* pfn_version(): bumped whenever an argument list changes           */
+#define PFN_VERSION 101         /* pfn_version(): bumped whenever the ABI changes (101: pfn_tiling)  */
 
 #define PFN_MAX_HIDDEN 8
 #define PFN_MAX_D 32            /* the d x d system is inverted by ONE workgroup: [d, 2d] float64 in LDS */
@@ -74,6 +74,21 @@ typedef struct pfn_adam {
     double lr, beta1, beta2, eps, weight_decay;
 } pfn_adam;
 
+/* pfn_tiling(): how the host tiles a batch / a pfn_forward call of `rows` rows.  A tile is the rows one workgroup
+ * stages in LDS; *_lds_bytes is the dynamic LDS its launch requests (above 65 536 the launch first raises the
+ * kernel's limit).  A tile of 0: that kernel cannot run this shape. */
+typedef struct pfn_tiling_info {
+    int32_t step_tile;                  /* R: batch rows per k_step workgroup                                    */
+    int32_t step_cap;                   /* the largest R that LDS and the 256 threads allow                      */
+    int32_t fwd_tile;                   /* pfn_forward                                                           */
+    int32_t reserved;
+    int64_t step_wgs;                   /* G = ceil(rows / R): workgroups, and partial-gradient slabs summed     */
+    int64_t step_wg_bound;              /* the G that pfn_workspace_bytes(rows) provides for: >= G of any batch
+                                           of at most `rows` rows                                               */
+    int64_t step_lds_bytes;
+    int64_t fwd_lds_bytes;
+} pfn_tiling_info;
+
 int         pfn_version(void);
 const char *pfn_status_string(int status);
 
@@ -82,6 +97,11 @@ int64_t pfn_param_count(const pfn_shape *s);
 
 /* workspace of a training call whose batches have at most batch_rows rows; 0 for an invalid shape */
 size_t pfn_workspace_bytes(const pfn_shape *s, int64_t batch_rows);
+
+/* Host only, launches nothing: the tiling of a training step on `rows` batch rows and of pfn_forward on `rows` rows,
+ * from the same functions the launches use.  PFN_EINVAL for a bad shape, rows < 1 or a NULL out; PFN_EUNSUPPORTED
+ * where the step cannot run (the step fields are then 0; fwd_* is still filled where pfn_forward can run). */
+int pfn_tiling(const pfn_shape *s, int64_t rows, pfn_tiling_info *out);
 
 /*
  * Net.forward over n rows.  Outputs (each [n, d], each nullable): mu, sigma, x_tilde, inv.

@@ -106,6 +106,30 @@ int64_t step_wg_bound(const NShape &w, int64_t batch_rows) {
     return a < b ? a : b;
 }
 
+// what one launch is made of: rows per workgroup, LDS bytes, workgroups.  enqueue_step / pfn_forward launch from these and
+// pfn_tiling reports them; tile == 0: the shape does not fit
+struct Plan {
+    int tile;
+    size_t lds;
+    int64_t wgs;
+};
+
+Plan step_plan(const NShape &w, int64_t rows) {
+    Plan p{step_tile(w, rows), 0, 0};
+    if (p.tile < 1) return Plan{0, 0, 0};
+    p.lds = (size_t)w.shared + (size_t)(p.tile + 1) * w.step_unit * sizeof(float);
+    p.wgs = (rows + p.tile - 1) / p.tile;
+    return p;
+}
+
+Plan fwd_plan(const NShape &w, int64_t n) {
+    Plan p{tile_cap(w, w.fwd_unit), 0, 0};
+    if (p.tile < 1) return Plan{0, 0, 0};
+    p.lds = (size_t)w.shared + (size_t)(p.tile + 1) * w.fwd_unit * sizeof(float);
+    p.wgs = (n + p.tile - 1) / p.tile;
+    return p;
+}
+
 struct Ws {
     float *gpart;    // [G][P]
     float *lpart;    // [G]
@@ -524,9 +548,10 @@ int big_lds(K kernel, size_t bytes, std::atomic<uint64_t> &done) {
 int enqueue_step(hipStream_t st, const NShape &w, float *params, float *m, float *v, const float *x, const float *c,
                  const int64_t *ri, int64_t rows, const rnvp::AdamK *adam, float *grad_out, float *loss_out,
                  int32_t *status, int first, const Ws &ws) {
-    const int R = step_tile(w, rows);
-    const int64_t G = (rows + R - 1) / R;
-    const size_t lds = (size_t)w.shared + (size_t)(R + 1) * w.step_unit * sizeof(float);
+    const Plan pl = step_plan(w, rows);
+    const int R = pl.tile;
+    const int64_t G = pl.wgs;
+    const size_t lds = pl.lds;
     if (int e = big_lds(k_step, lds, g_lds_step)) return e;
     const float Bd = (float)rows * (float)w.d;
     hipLaunchKernelGGL(k_step, dim3((unsigned)G), dim3(NT), lds, st, w, R, params, x, c, ri, rows, 1.0f / Bd, ws.gpart,
@@ -582,16 +607,33 @@ size_t pfn_workspace_bytes(const pfn_shape *s, int64_t batch_rows) {
     return ws_bytes(w, batch_rows, nullptr, nullptr);
 }
 
+int pfn_tiling(const pfn_shape *s, int64_t rows, pfn_tiling_info *out) {
+    NShape w;
+    const int e = make_nshape(s, w);
+    if (e == PFN_EINVAL || !out || rows < 1) return PFN_EINVAL;
+    memset(out, 0, sizeof(*out));
+    if (e) return e;
+    const Plan fw = fwd_plan(w, rows);
+    out->fwd_tile = fw.tile; out->fwd_lds_bytes = (int64_t)fw.lds;
+    out->step_cap = tile_cap(w, w.step_unit);
+    if (out->step_cap < 1) return PFN_EUNSUPPORTED;
+    const Plan st = step_plan(w, rows);
+    out->step_tile = st.tile; out->step_wgs = st.wgs; out->step_lds_bytes = (int64_t)st.lds;
+    out->step_wg_bound = step_wg_bound(w, rows);
+    return PFN_OK;
+}
+
 int pfn_forward(void *stream, const pfn_shape *s, const float *params, const float *c, const float *eps,
                 const float *x, int64_t n, float *mu, float *sigma, float *x_tilde, float *inv, int32_t *status) {
     NShape w;
     if (int e = make_nshape(s, w)) return e;
-    const int T = tile_cap(w, w.fwd_unit);
-    if (T < 1) return PFN_EUNSUPPORTED;
+    if (tile_cap(w, w.fwd_unit) < 1) return PFN_EUNSUPPORTED;
     if (!params || !c || n < 1 || (x_tilde && !eps) || (inv && !x)) return PFN_EINVAL;
-    const size_t lds = (size_t)w.shared + (size_t)(T + 1) * w.fwd_unit * sizeof(float);
+    const Plan pl = fwd_plan(w, n);
+    const int T = pl.tile;
+    const size_t lds = pl.lds;
     if (int e = big_lds(k_forward, lds, g_lds_fwd)) return e;
-    hipLaunchKernelGGL(k_forward, dim3((unsigned)((n + T - 1) / T)), dim3(NT), lds, (hipStream_t)stream, w, T, params, c,
+    hipLaunchKernelGGL(k_forward, dim3((unsigned)pl.wgs), dim3(NT), lds, (hipStream_t)stream, w, T, params, c,
                        eps, x, n, mu, sigma, x_tilde, inv, status);
     RNVP_HIP_TRY(hipGetLastError());
     return PFN_OK;

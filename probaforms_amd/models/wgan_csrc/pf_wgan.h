@@ -43,7 +43,7 @@ extern "C" {
 #define PFW_EUNSUPPORTED (-2)   /* one row's working set does not fit the 160 KiB of LDS        */
 #define PFW_EWORKSPACE   (-3)   /* workspace smaller than pfw_workspace_bytes() says            */
 
-#define PFW_VERSION 100         /* pfw_version(): bumped whenever an argument list changes      */
+#define PFW_VERSION 101         /* pfw_version(): bumped whenever the ABI changes (101: pfw_tiling) */
 
 #define PFW_MAX_HIDDEN 8
 #define PFW_ACT_TANH 0          /* the values of RNVP_ACT_* (include/rnvp_hip.h)                  */
@@ -74,6 +74,25 @@ typedef struct pfw_rmsprop {
     double lr, alpha, eps, weight_decay, clamp;
 } pfw_rmsprop;
 
+/* pfw_tiling(): how the host tiles a batch / an inference call of `rows` rows.  A tile is the rows one workgroup
+ * stages in LDS; *_lds_bytes is the dynamic LDS its launch requests (above 65 536 the launch first raises the
+ * kernel's limit).  A tile of 0: that kernel cannot run this shape. */
+typedef struct pfw_tiling_info {
+    int32_t step_tile;                  /* R: batch rows per k_step workgroup (a critic step stages 2R LDS rows) */
+    int32_t step_cap;                   /* the largest R that LDS and the 256 threads allow                      */
+    int32_t eloss_tile;                 /* pfw_epoch_losses                                                      */
+    int32_t gen_tile;                   /* pfw_generate                                                          */
+    int32_t crit_tile;                  /* pfw_critic                                                            */
+    int32_t reserved;
+    int64_t step_wgs;                   /* G = ceil(rows / R): workgroups, and partial-gradient slabs summed     */
+    int64_t step_wg_bound;              /* the G that pfw_workspace_bytes(rows) provides for: >= G of any batch
+                                           of at most `rows` rows                                               */
+    int64_t step_lds_bytes;
+    int64_t eloss_lds_bytes;
+    int64_t gen_lds_bytes;
+    int64_t crit_lds_bytes;
+} pfw_tiling_info;
+
 int         pfw_version(void);
 const char *pfw_status_string(int status);
 
@@ -83,6 +102,11 @@ int64_t pfw_param_count(const pfw_shape *s, int net);
 /* workspace of a training call whose batches have at most batch_rows rows and whose epoch-end
  * losses run over loss_rows rows (0 when none are computed) */
 size_t pfw_workspace_bytes(const pfw_shape *s, int64_t batch_rows, int64_t loss_rows);
+
+/* Host only, launches nothing: the tiling of a training step on `rows` batch rows and of the inference calls on
+ * `rows` rows, from the same functions the launches use.  PFW_EINVAL for a bad shape, rows < 1 or a NULL out;
+ * PFW_EUNSUPPORTED where the step cannot run (the step fields are then 0; the inference fields are still filled). */
+int pfw_tiling(const pfw_shape *s, int64_t rows, pfw_tiling_info *out);
 
 /* out [n, d] = G([z || c]) */
 int pfw_generate(void *stream, const pfw_shape *s, const float *params, const float *z, const float *c,

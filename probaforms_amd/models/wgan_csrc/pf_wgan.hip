@@ -132,6 +132,39 @@ int fwd_tile(int unit) {
     return (int)(T > FWD_T ? FWD_T : (T < 0 ? 0 : T));
 }
 
+// what one launch is made of: rows per workgroup, LDS bytes, workgroups.  enqueue_* / pfw_generate / pfw_critic launch from
+// these and pfw_tiling reports them; tile == 0: the shape does not fit
+struct Plan {
+    int tile;
+    size_t lds;
+    int64_t wgs;
+};
+
+Plan step_plan(const WShape &w, int64_t rows) {
+    Plan p{step_tile(w, rows), 0, 0};
+    if (p.tile < 1) return Plan{0, 0, 0};
+    p.lds = (size_t)(2 * p.tile + 1) * w.step_unit * sizeof(float);
+    p.wgs = (rows + p.tile - 1) / p.tile;
+    return p;
+}
+
+Plan eloss_plan(const WShape &w, int64_t n) {
+    Plan p{eloss_tile(w), 0, 0};
+    if (p.tile < 1) return Plan{0, 0, 0};
+    p.lds = (size_t)(2 * p.tile + 1) * w.fwd_unit * sizeof(float);
+    p.wgs = (n + p.tile - 1) / p.tile;
+    return p;
+}
+
+// pfw_generate (unit = gen_unit) / pfw_critic (unit = crit_unit)
+Plan fwd_plan(int unit, int64_t n) {
+    Plan p{fwd_tile(unit), 0, 0};
+    if (p.tile < 1) return Plan{0, 0, 0};
+    p.lds = (size_t)(p.tile + 1) * unit * sizeof(float);
+    p.wgs = (n + p.tile - 1) / p.tile;
+    return p;
+}
+
 struct Ws {
     float *gpart;   // [G][PG + PD]
     float *lpart;   // [G]
@@ -394,10 +427,10 @@ std::atomic<uint64_t> g_lds_step{0}, g_lds_eloss{0}, g_lds_gen{0}, g_lds_crit{0}
 int enqueue_step(hipStream_t st, const WShape &w, int kind, float *params, float *sq, const float *x, const float *c,
                  const int64_t *ri, const float *z, int64_t rows, const Rms *rms, float *grad_out, float *loss_out,
                  const Ws &ws) {
-    const int R = step_tile(w, rows);
-    const int S = 2 * R + 1;
-    const int64_t G = (rows + R - 1) / R;
-    const size_t lds = (size_t)S * w.step_unit * sizeof(float);
+    const Plan pl = step_plan(w, rows);
+    const int R = pl.tile;
+    const int64_t G = pl.wgs;
+    const size_t lds = pl.lds;
     const bool critic = kind == PFW_STEP_CRITIC;
     if (int e = big_lds(k_step, lds, g_lds_step)) return e;
     hipLaunchKernelGGL(k_step, dim3((unsigned)G), dim3(NT), lds, st, w, critic ? 1 : 0, R, params, x, c, ri, z, rows,
@@ -414,9 +447,10 @@ int enqueue_step(hipStream_t st, const WShape &w, int kind, float *params, float
 
 int enqueue_eloss(hipStream_t st, const WShape &w, const float *params, const float *x, const float *c, const float *z,
                   int64_t n, float *out, const Ws &ws) {
-    const int T = eloss_tile(w);
-    const size_t lds = (size_t)(2 * T + 1) * w.fwd_unit * sizeof(float);
-    const int64_t E = (n + T - 1) / T;
+    const Plan pl = eloss_plan(w, n);
+    const int T = pl.tile;
+    const size_t lds = pl.lds;
+    const int64_t E = pl.wgs;
     if (int e = big_lds(k_eloss, lds, g_lds_eloss)) return e;
     hipLaunchKernelGGL(k_eloss, dim3((unsigned)E), dim3(2 * FWD_T), lds, st, w, T, params, x, c, z, n, ws.epart);
     RNVP_HIP_TRY(hipGetLastError());
@@ -459,16 +493,34 @@ size_t pfw_workspace_bytes(const pfw_shape *s, int64_t batch_rows, int64_t loss_
     return ws_bytes(w, batch_rows, loss_rows, nullptr, nullptr);
 }
 
+int pfw_tiling(const pfw_shape *s, int64_t rows, pfw_tiling_info *out) {
+    WShape w;
+    if (int e = make_wshape(s, w)) return e;
+    if (!out || rows < 1) return PFW_EINVAL;
+    memset(out, 0, sizeof(*out));
+    const Plan el = eloss_plan(w, rows), ge = fwd_plan(gen_unit(w), rows), cr = fwd_plan(crit_unit(w), rows);
+    out->eloss_tile = el.tile; out->eloss_lds_bytes = (int64_t)el.lds;
+    out->gen_tile = ge.tile; out->gen_lds_bytes = (int64_t)ge.lds;
+    out->crit_tile = cr.tile; out->crit_lds_bytes = (int64_t)cr.lds;
+    out->step_cap = step_tile_cap(w);
+    if (out->step_cap < 1) return PFW_EUNSUPPORTED;
+    const Plan st = step_plan(w, rows);
+    out->step_tile = st.tile; out->step_wgs = st.wgs; out->step_lds_bytes = (int64_t)st.lds;
+    out->step_wg_bound = step_wg_bound(w, rows);
+    return PFW_OK;
+}
+
 int pfw_generate(void *stream, const pfw_shape *s, const float *params, const float *z, const float *c, int64_t n,
                  float *out) {
     WShape w;
     if (int e = make_wshape(s, w)) return e;
     if (!params || !z || !out || n < 1 || (w.c > 0 && !c)) return PFW_EINVAL;
-    const int T = fwd_tile(gen_unit(w));
+    const Plan pl = fwd_plan(gen_unit(w), n);
+    const int T = pl.tile;
     if (T < 1) return PFW_EUNSUPPORTED;
-    const size_t lds = (size_t)(T + 1) * gen_unit(w) * sizeof(float);
+    const size_t lds = pl.lds;
     if (int e = big_lds(k_generate, lds, g_lds_gen)) return e;
-    hipLaunchKernelGGL(k_generate, dim3((unsigned)((n + T - 1) / T)), dim3(FWD_T), lds, (hipStream_t)stream, w, T, params,
+    hipLaunchKernelGGL(k_generate, dim3((unsigned)pl.wgs), dim3(FWD_T), lds, (hipStream_t)stream, w, T, params,
                        z, c, n, out);
     RNVP_HIP_TRY(hipGetLastError());
     return PFW_OK;
@@ -479,11 +531,12 @@ int pfw_critic(void *stream, const pfw_shape *s, const float *params, const floa
     WShape w;
     if (int e = make_wshape(s, w)) return e;
     if (!params || !x || !out || n < 1 || (w.c > 0 && !c)) return PFW_EINVAL;
-    const int T = fwd_tile(crit_unit(w));
+    const Plan pl = fwd_plan(crit_unit(w), n);
+    const int T = pl.tile;
     if (T < 1) return PFW_EUNSUPPORTED;
-    const size_t lds = (size_t)(T + 1) * crit_unit(w) * sizeof(float);
+    const size_t lds = pl.lds;
     if (int e = big_lds(k_critic, lds, g_lds_crit)) return e;
-    hipLaunchKernelGGL(k_critic, dim3((unsigned)((n + T - 1) / T)), dim3(FWD_T), lds, (hipStream_t)stream, w, T, params,
+    hipLaunchKernelGGL(k_critic, dim3((unsigned)pl.wgs), dim3(FWD_T), lds, (hipStream_t)stream, w, T, params,
                        x, c, n, out);
     RNVP_HIP_TRY(hipGetLastError());
     return PFW_OK;

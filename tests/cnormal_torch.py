@@ -6,12 +6,15 @@ bias, in module order model.*, mu, log_sigma, out."""
 import numpy as np
 import torch
 
+from restatement_ops import affine
+
 ACTS = {'tanh': torch.tanh, 'relu': torch.relu, 'sigmoid': torch.sigmoid}
 
 
 class Normal:
-    def __init__(self, d, c, hidden=(10,), activation='tanh', independent=False):
+    def __init__(self, d, c, hidden=(10,), activation='tanh', independent=False, sequential=False):
         self.d, self.c, self.hidden, self.independent = d, c, tuple(hidden), bool(independent)
+        self.sequential = sequential
         self.act = ACTS.get(activation, torch.relu)           # anything else means ReLU
         w = list(zip([c] + list(hidden[:-1]), hidden))
         self.trunk = w
@@ -32,14 +35,14 @@ class Normal:
         trunk, (Wm, bm), (Wl, bl), (Wo, bo) = self.split(flat)
         h = C
         for W, b in trunk:
-            h = self.act(h @ W.T + b)
-        mu = h @ Wm.T + bm
-        sigma = torch.exp(h @ Wl.T + bl)
+            h = self.act(affine(h, W, b, self.sequential))
+        mu = affine(h, Wm, bm, self.sequential)
+        sigma = torch.exp(affine(h, Wl, bl, self.sequential))
         xt = None
         if eps is not None:
             xt = mu + eps * sigma
             if not self.independent:
-                xt = xt @ Wo.T + bo
+                xt = affine(xt, Wo, bo, self.sequential)
         inv = None if X is None else (X - bo) @ torch.linalg.inv(Wo.T)
         return xt, inv, mu, sigma
 

@@ -21,6 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import cnormal_torch as ct  # noqa: E402
 import hygiene  # noqa: E402
+from parity import parity  # noqa: E402
 from test_cnormal_host import NAMES, cond_of, fixture_batches, load, restatement  # noqa: E402
 from probaforms_amd.models import _cnormal_lib as N  # noqa: E402
 from probaforms_amd.models.cnormal import ConditionalNormal, Net  # noqa: E402
@@ -31,21 +32,10 @@ if not os.path.exists(N.LIB_PATH):    # tests/conftest.py builds only librnvp_hi
     subprocess.check_call(["make", "-C", os.path.dirname(N.LIB_PATH), "-s"])
 
 DEV = torch.device("cuda")
-EPS32 = float(np.finfo(np.float32).eps)
 
 
 def dev(a, dtype=torch.float32):
     return None if a is None else torch.as_tensor(np.ascontiguousarray(a), dtype=dtype).to(DEV)
-
-
-def parity(case, what, got, ref32, ref64):
-    """assert |got - ref64| <= max(4 e_ref, 4 ulp of the magnitude), e_ref = |ref32 - ref64|; max norms"""
-    got, ref32, ref64 = (np.asarray(a, np.float64) for a in (got, ref32, ref64))
-    e_ref = float(np.abs(ref32 - ref64).max())
-    err = float(np.abs(got - ref64).max())
-    floor = 4 * EPS32 * float(np.abs(ref64).max())
-    print("PARITY %-14s %-22s e_ref %.3e  gpu %.3e  bound %.3e" % (case, what, e_ref, err, max(4 * e_ref, floor)))
-    assert err <= max(4 * e_ref, floor), (case, what, err, e_ref, floor)
 
 
 def model_of(kw, X, C, params=None):

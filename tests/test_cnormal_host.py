@@ -148,6 +148,25 @@ def test_shape_struct_matches_the_c_header():
     assert v[7:] == [N.ABI_VERSION, N.MAX_HIDDEN, N.MAX_D, N.ACT_TANH, N.ACT_RELU, N.ACT_SIGMOID, N.EUNSUPPORTED]
 
 
+def test_tiling_struct_matches_the_c_header():
+    T = N.TilingInfo
+    names = [n for n, _ in T._fields_]
+    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "pf_cnormal.h"\n'
+           'int main(void){printf("%zu", sizeof(pfn_tiling_info));\n' +
+           "".join('printf(" %%zu %%zu", offsetof(pfn_tiling_info, %s), sizeof(((pfn_tiling_info *)0)->%s));\n' % (n, n)
+                   for n in names) + 'return 0;}\n')
+    with tempfile.TemporaryDirectory() as td:
+        c = os.path.join(td, "s.c"); exe = os.path.join(td, "s")
+        open(c, "w").write(src)
+        subprocess.check_call(["gcc", "-std=c99", "-I", os.path.dirname(HEADER), c, "-o", exe])
+        v = list(map(int, subprocess.check_output([exe]).split()))
+    assert v[0] == ctypes.sizeof(T)
+    assert v[1:] == [x for n in names for x in (getattr(T, n).offset, getattr(T, n).size)]
+    declared = re.search(r"typedef struct pfn_tiling_info \{(.*?)\} pfn_tiling_info;", open(HEADER).read(), flags=re.S).group(1)
+    declared = re.sub(r"/\*.*?\*/", "", declared, flags=re.S)
+    assert re.findall(r"int(?:32|64)_t\s+(\w+);", declared) == names            # every field, in order
+
+
 def test_header_declarations_equal_the_binding_exports():
     text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
     declared = re.findall(r"\b(pfn_[a-z_]+)\s*\(", text)

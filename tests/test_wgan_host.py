@@ -76,6 +76,26 @@ def test_shape_struct_matches_the_c_header():
                      W.EUNSUPPORTED]
 
 
+def test_tiling_struct_matches_the_c_header():
+    from probaforms_amd.models import _wgan_lib as W
+    T = W.TilingInfo
+    names = [n for n, _ in T._fields_]
+    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "pf_wgan.h"\n'
+           'int main(void){printf("%zu", sizeof(pfw_tiling_info));\n' +
+           "".join('printf(" %%zu %%zu", offsetof(pfw_tiling_info, %s), sizeof(((pfw_tiling_info *)0)->%s));\n' % (n, n)
+                   for n in names) + 'return 0;}\n')
+    with tempfile.TemporaryDirectory() as td:
+        c = os.path.join(td, "s.c"); exe = os.path.join(td, "s")
+        open(c, "w").write(src)
+        subprocess.check_call(["gcc", "-std=c99", "-I", os.path.dirname(HEADER), c, "-o", exe])
+        v = list(map(int, subprocess.check_output([exe]).split()))
+    assert v[0] == ctypes.sizeof(T)
+    assert v[1:] == [x for n in names for x in (getattr(T, n).offset, getattr(T, n).size)]
+    declared = re.search(r"typedef struct pfw_tiling_info \{(.*?)\} pfw_tiling_info;", open(HEADER).read(), flags=re.S).group(1)
+    declared = re.sub(r"/\*.*?\*/", "", declared, flags=re.S)
+    assert re.findall(r"int(?:32|64)_t\s+(\w+);", declared) == names            # every field, in order
+
+
 def test_header_declarations_equal_the_binding_exports():
     from probaforms_amd.models import _wgan_lib as W
     text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)

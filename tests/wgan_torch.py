@@ -4,6 +4,8 @@ of a fit, and a whole fit.  Parameters are flat: every nn.Linear's weight then b
 import numpy as np
 import torch
 
+from restatement_ops import affine
+
 
 def widths(n_in, hidden, n_out):
     return list(zip([n_in] + list(hidden), list(hidden) + [n_out]))
@@ -14,10 +16,11 @@ def n_params(n_in, hidden, n_out):
 
 
 class Net:
-    def __init__(self, n_in, hidden, n_out, act):
+    def __init__(self, n_in, hidden, n_out, act, sequential=False):
         self.w = widths(n_in, hidden, n_out)
         self.act = act
         self.P = n_params(n_in, hidden, n_out)
+        self.sequential = sequential
 
     def split(self, flat):
         out, off = [], 0
@@ -30,7 +33,7 @@ class Net:
     def __call__(self, flat, x):
         layers = self.split(flat)
         for k, (W, b) in enumerate(layers):
-            x = x @ W.T + b
+            x = affine(x, W, b, self.sequential)
             if k < len(layers) - 1:
                 x = torch.tanh(x) if self.act == 'tanh' else torch.relu(x)
         return x
@@ -39,23 +42,23 @@ class Net:
 class Wgan:
     """the two nets of one shape; G: latent + c -> d, D: d + c -> 1"""
 
-    def __init__(self, d, c, latent, g_hidden, d_hidden, g_act='relu', d_act='relu'):
+    def __init__(self, d, c, latent, g_hidden, d_hidden, g_act='relu', d_act='relu', sequential=False):
         self.d, self.c, self.latent = d, c, latent
-        self.G = Net(latent + c, g_hidden, d, g_act)
-        self.D = Net(d + c, d_hidden, 1, d_act)
+        self.G = Net(latent + c, g_hidden, d, g_act, sequential)
+        self.D = Net(d + c, d_hidden, 1, d_act, sequential)
         self.PG, self.PD = self.G.P, self.D.P
 
     @staticmethod
     def _cat(a, c):
         return a if c is None or c.shape[1] == 0 else torch.cat([a, c], 1)
 
-    def loss_grad(self, params, X, C, rows, z, kind):
-        """(loss, gradient of the stepped net) in float64; kind 1 = critic step, 0 = generator step"""
-        p = torch.tensor(np.asarray(params[:self.PG + self.PD], np.float64), requires_grad=True)
+    def loss_grad(self, params, X, C, rows, z, kind, dtype=torch.float64):
+        """(loss, gradient of the stepped net) in `dtype`; kind 1 = critic step, 0 = generator step"""
+        p = torch.tensor(np.asarray(params[:self.PG + self.PD]), dtype=dtype, requires_grad=True)
         pG, pD = p[:self.PG], p[self.PG:]
-        x = torch.tensor(np.asarray(X)[rows], dtype=torch.float64)
-        c = None if C is None or np.asarray(C).shape[1] == 0 else torch.tensor(np.asarray(C)[rows], dtype=torch.float64)
-        fake = self.G(pG, self._cat(torch.tensor(np.asarray(z), dtype=torch.float64), c))
+        x = torch.tensor(np.asarray(X)[rows], dtype=dtype)
+        c = None if C is None or np.asarray(C).shape[1] == 0 else torch.tensor(np.asarray(C)[rows], dtype=dtype)
+        fake = self.G(pG, self._cat(torch.tensor(np.asarray(z), dtype=dtype), c))
         if kind == 1:
             loss = -self.D(pD, self._cat(x, c)).mean() + self.D(pD, self._cat(fake, c)).mean()
         else:
@@ -79,24 +82,24 @@ class Wgan:
             out = max(out, float(g[self.PG:].abs().max()))
         return out
 
-    def epoch_losses(self, params, X, C, Z):
-        p = torch.tensor(np.asarray(params[:self.PG + self.PD], np.float64))
-        x = torch.tensor(np.asarray(X), dtype=torch.float64)
-        c = None if C is None or np.asarray(C).shape[1] == 0 else torch.tensor(np.asarray(C), dtype=torch.float64)
-        fake = self.G(p[:self.PG], self._cat(torch.tensor(np.asarray(Z), dtype=torch.float64), c))
+    def epoch_losses(self, params, X, C, Z, dtype=torch.float64):
+        p = torch.tensor(np.asarray(params[:self.PG + self.PD]), dtype=dtype)
+        x = torch.tensor(np.asarray(X), dtype=dtype)
+        c = None if C is None or np.asarray(C).shape[1] == 0 else torch.tensor(np.asarray(C), dtype=dtype)
+        fake = self.G(p[:self.PG], self._cat(torch.tensor(np.asarray(Z), dtype=dtype), c))
         gen = -self.D(p[self.PG:], self._cat(fake, c)).mean()
         disc = self.D(p[self.PG:], self._cat(x, c)).mean() + gen
         return float(gen), float(disc)
 
-    def generate(self, params, Z, C):
-        p = torch.tensor(np.asarray(params[:self.PG], np.float64))
-        c = None if C is None else torch.tensor(np.asarray(C), dtype=torch.float64)
-        return self.G(p, self._cat(torch.tensor(np.asarray(Z), dtype=torch.float64), c)).numpy()
+    def generate(self, params, Z, C, dtype=torch.float64):
+        p = torch.tensor(np.asarray(params[:self.PG]), dtype=dtype)
+        c = None if C is None else torch.tensor(np.asarray(C), dtype=dtype)
+        return self.G(p, self._cat(torch.tensor(np.asarray(Z), dtype=dtype), c)).numpy()
 
-    def critic(self, params, X, C):
-        p = torch.tensor(np.asarray(params[self.PG:self.PG + self.PD], np.float64))
-        c = None if C is None else torch.tensor(np.asarray(C), dtype=torch.float64)
-        return self.D(p, self._cat(torch.tensor(np.asarray(X), dtype=torch.float64), c)).numpy()
+    def critic(self, params, X, C, dtype=torch.float64):
+        p = torch.tensor(np.asarray(params[self.PG:self.PG + self.PD]), dtype=dtype)
+        c = None if C is None else torch.tensor(np.asarray(C), dtype=dtype)
+        return self.D(p, self._cat(torch.tensor(np.asarray(X), dtype=dtype), c)).numpy()
 
 
 def rmsprop_f32(p, g, v, lr, alpha=0.99, eps=1e-8, wd=0.0, clamp=0.0):
