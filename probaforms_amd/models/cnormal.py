@@ -199,3 +199,19 @@ class ConditionalNormal(GenModel):
             C = torch.zeros(C, 1)                   # meaningful only after fit(X, None)   (cnormal.py:236)
         x_tilde, _, _, _ = self.model(None, C)
         return x_tilde.cpu().detach().numpy()
+
+    def sample_many(self, C=100, n_draws=100):
+        """``np.array([self.sample(C) for _ in range(n_draws)])`` -> float32 numpy [n_draws, n, d] (a name the reference does
+        not have): the trunk runs once per condition row, the draws are one launch per window of draws.  Consumes torch's
+        global CPU generator exactly as the loop does."""
+        from . import _gendraw
+        return _gendraw.sample_many(self, C, n_draws)
+
+    def sample_stats(self, C=100, n_draws=100, quantiles=None, ddof=0):
+        """Predictive statistics per condition row over ``n_draws`` samples, as ``RealNVP.sample_stats``:
+        ``SampleStats(mean, std, min, max, quantiles)`` of float32 numpy arrays [n, d] (quantiles [Q, n, d], numpy's 'linear'
+        method, or None).  eps comes from torch's global CPU generator exactly as ``n_draws`` successive ``sample(C)`` calls
+        draw it; mu and sigma are computed once per row, the draws and the reductions across them run on the device.
+        ``n_draws < 1``, a probability outside [0, 1] or quantiles with ``n_draws > 8192`` raise ValueError."""
+        from . import _gendraw
+        return _gendraw.sample_stats(self, C, n_draws, quantiles, ddof)

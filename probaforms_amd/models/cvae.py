@@ -431,3 +431,20 @@ class CVAE(GenModel):
             Z = torch.normal(0, 1, (C, self.lat_size))
             X = self.decoder(Z, None)
         return X.cpu().detach().numpy()
+
+    def sample_many(self, C=10, n_draws=100):
+        """``np.array([self.sample(C) for _ in range(n_draws)])`` -> float32 numpy [n_draws, n, d] (a name the reference does
+        not have): the draws of the notebooks' predictive loop in one launch per window of draws.  Consumes torch's global
+        CPU generator exactly as the loop does.  A decoder the kernel does not hold in LDS runs the loop itself."""
+        from . import _gendraw
+        return _gendraw.sample_many(self, C, n_draws)
+
+    def sample_stats(self, C=10, n_draws=100, quantiles=None, ddof=0):
+        """Predictive statistics per condition row over ``n_draws`` samples, as ``RealNVP.sample_stats``:
+        ``SampleStats(mean, std, min, max, quantiles)`` of float32 numpy arrays [n, d] (quantiles [Q, n, d], numpy's 'linear'
+        method, or None).  The latent draws come from torch's global CPU generator exactly as ``n_draws`` successive
+        ``sample(C)`` calls draw them; the decoder and the reductions across the draws run on the device.  ``n_draws < 1``,
+        a probability outside [0, 1] or quantiles with ``n_draws > 8192`` raise ValueError.  A decoder the kernel does not
+        hold in LDS falls back to the loop on the host (``self.sample`` n_draws times plus numpy)."""
+        from . import _gendraw
+        return _gendraw.sample_stats(self, C, n_draws, quantiles, ddof)
