@@ -14,7 +14,8 @@ those of models/_predict.py.
 import torch
 
 from . import _predict
-from ._predict import SampleStats, _chunk_quantiles, draw_windows, loop_draws, quantile_row_chunks, stats_of_draws, validate
+from ._predict import (SampleScores, SampleStats, ScoreSink, _chunk_quantiles, draw_windows, loop_draws, quantile_row_chunks,
+                       scores_of_draws, stats_of_draws, targets_on_host, validate, validate_scores)
 
 
 def one_stream(n, width):
@@ -84,10 +85,12 @@ class AffineJob:
                                        k_lo, k_cnt, K, state, x_out, xt)
 
 
-def run(job, Cd, n, K, probs, ddof, want_stats, want_draws):
+def run(job, Cd, n, K, probs, ddof, want_stats, want_draws, scores=None):
     """-> (SampleStats of device tensors or None, draws [K, n, d] device tensor or None).  The caller has asked
     job.supported().  Quantiles may force row chunks; every chunk then walks the same K noise draws (the generator is
-    rewound), so the draws are not kept in that case (want_draws and quantiles are separate public calls)."""
+    rewound), so the draws are not kept in that case (want_draws and quantiles are separate public calls).
+    scores = (Y, fair): the scores path -- neither statistics nor draws; only the transposed draws are kept, per row chunk,
+    and the first item returned is a SampleScores of device tensors."""
     from . import _predict_lib as pl
     dev, d, width = job.device, job.d, job.width
     f32 = dict(dtype=torch.float32, device=dev)
@@ -96,7 +99,12 @@ def run(job, Cd, n, K, probs, ddof, want_stats, want_draws):
     state = pl.new_state(n, d, dev) if want_stats else None
     q_out = torch.empty((len(probs), n, d), **f32) if want_q else None
     probs_dev = torch.tensor(probs, dtype=torch.float64, device=dev) if want_q else None
-    chunks = quantile_row_chunks(n, d, K, _predict.XT_CHUNK_BYTES) if want_q else ([(0, n)] if n else [])
+    sink = None
+    if scores is not None:
+        assert not (want_stats or want_draws)
+        sink = ScoreSink(scores[0], n, d, K, probs, scores[1], dev)
+    want_xt = want_q or sink is not None
+    chunks = quantile_row_chunks(n, d, K, _predict.XT_CHUNK_BYTES) if want_xt else ([(0, n)] if n else [])
     assert not (want_draws and len(chunks) > 1)
     if n > 0:
         windows = draw_windows(K, n, width, _predict.Z_WINDOW_BYTES)
@@ -105,12 +113,14 @@ def run(job, Cd, n, K, probs, ddof, want_stats, want_draws):
         for ci, (lo, m) in enumerate(chunks):
             if ci > 0:
                 torch.set_rng_state(start)                        # every row chunk walks the same K draws
-            xt = torch.empty((m, d, K), **f32) if want_q else None
+            xt = torch.empty((m, d, K), **f32) if want_xt else None
             for k_lo, k_cnt in windows:
                 zw = noise(k_cnt, n, width).to(dev)               # one upload per window
                 job.launch(lo, m, n, zw, k_lo, k_cnt, K, None if state is None else state[lo:lo + m],
                            None if x_out is None else x_out[k_lo:k_lo + k_cnt], xt)
-            if xt is not None:
+            if sink is not None:
+                sink.chunk(pl, xt, lo, m)
+            elif xt is not None:
                 _chunk_quantiles(pl, xt, lo, m, d, K, probs_dev, q_out)
     stats = None
     if want_stats:
@@ -118,6 +128,8 @@ def run(job, Cd, n, K, probs, ddof, want_stats, want_draws):
         if n > 0:
             pl.finalize(state, n, d, ddof, mean, std, mn, mx)
         stats = SampleStats(mean, std, mn, mx, q_out)
+    if sink is not None:
+        return sink.result(), None
     return stats, x_out
 
 
@@ -188,3 +200,14 @@ def sample_stats(model, C, n_draws, quantiles, ddof):
     n, Cd = conditions(C)
     s = run(job, Cd, n, K, probs, int(ddof), True, False)[0]
     return SampleStats(*(None if a is None else a.cpu().numpy() for a in s))
+
+
+def sample_scores(model, C, Y, n_draws, quantiles, fair):
+    """SampleScores of float32 numpy arrays: n_draws samples per condition row scored against the observed targets Y"""
+    K, probs = validate_scores(n_draws, quantiles)
+    job, conditions = job_of(model)
+    if not job.supported():
+        return scores_of_draws(loop_draws(model.sample, C, K), targets_on_host(Y), probs, fair)
+    n, Cd = conditions(C)
+    s = run(job, Cd, n, K, probs, 0, False, False, scores=(Y, fair))[0]
+    return SampleScores(*(None if a is None else a.cpu().numpy() for a in s))

@@ -7,6 +7,9 @@ What the reference's notebooks do by hand (docs/examples/regression.ipynb, forec
 -- as one call: libpf_predict.so (predict_csrc/pf_predict.h) draws the K prior samples per condition row, pushes them through
 the inverse flow and reduces across the draws on the device; only [n, d] statistics leave it.
 
+``sample_scores`` scores those draws against observed targets (CRPS, PIT, quantiles, pinball loss; pfp_scores): the same draws,
+the same sort, one more pass over each sorted series.
+
 The arithmetic that needs no GPU lives here as plain functions (argument validation, the draw windows, the row chunks, the
 routing between the kernels and the host loop) so that the CPU suite covers it.
 """
@@ -20,6 +23,7 @@ XT_CHUNK_BYTES = 1 << 30          # the transposed draws the quantile kernel sor
 MAX_QUANTILE_DRAWS = 8192         # pf_predict.h PFP_MAX_QUANTILE_DRAWS
 
 SampleStats = collections.namedtuple("SampleStats", "mean std min max quantiles")
+SampleScores = collections.namedtuple("SampleScores", "crps pit quantiles pinball")
 
 
 def validate(n_draws, quantiles=None, ddof=0):
@@ -44,6 +48,16 @@ def validate(n_draws, quantiles=None, ddof=0):
         if K > MAX_QUANTILE_DRAWS:
             raise ValueError("quantiles need n_draws <= %d (one series is sorted inside one workgroup), got %d"
                              % (MAX_QUANTILE_DRAWS, K))
+    return K, probs
+
+
+def validate_scores(n_draws, quantiles=None):
+    """-> (K, probs) as validate(); the series is always sorted, so n_draws > MAX_QUANTILE_DRAWS raises ValueError with or
+    without quantiles"""
+    K, probs = validate(n_draws, quantiles)
+    if K > MAX_QUANTILE_DRAWS:
+        raise ValueError("sample_scores needs n_draws <= %d (one series is sorted inside one workgroup), got %d"
+                         % (MAX_QUANTILE_DRAWS, K))
     return K, probs
 
 
@@ -91,6 +105,92 @@ def stats_of_draws(X, probs, ddof):
         return SampleStats(f(X64.mean(axis=0)), f(std), f(X64.min(axis=0)), f(X64.max(axis=0)), q)
 
 
+def scores_of_draws(X, Y, probs, fair):
+    """SampleScores (float32 numpy) of stacked draws X [K, n, d] against the targets Y [n, d]: the host route of
+    ``sample_scores``.  Per (row, column) series x_1 .. x_K and target y, in float64 with one rounding (D = K - 1 if fair
+    else K):
+        crps    = 1/K sum_k |x_k - y| - 1/(2 K D) sum_k sum_l |x_k - x_l|    (pair sum = 2 sum_i (2 i - K + 1) x_(i), sorted)
+        pit     = (#{x_k < y} + 0.5 #{x_k == y}) / K
+        pinball = (y - Q) (p - [y < Q]),  Q = numpy.quantile(x, p)
+    A NaN in the series or in y: crps, pit and pinball NaN (quantiles only for a NaN in the series).  A series holding an
+    infinity: crps NaN, as the pair sum's inf - inf gives."""
+    X64 = np.asarray(X, dtype=np.float32).astype(np.float64)
+    Y32 = np.asarray(Y, dtype=np.float32)
+    if X64.ndim != 3 or Y32.shape != X64.shape[1:]:
+        raise ValueError("Y must have shape %s (one target per condition row and column), got %s"
+                         % (X64.shape[1:], Y32.shape))
+    Y64 = Y32.astype(np.float64)
+    K = X64.shape[0]
+    f = lambda a: np.asarray(a, dtype=np.float32)
+    with np.errstate(all="ignore"):
+        nan = np.isnan(X64).any(axis=0)
+        bad = nan | np.isnan(Y64)
+        S = np.sort(X64, axis=0)
+        mid = S[K // 2]
+        mid = np.where(np.isfinite(mid), mid, 0.0)
+        w = (2.0 * np.arange(K) - K + 1.0).reshape((K,) + (1,) * (X64.ndim - 1))
+        s1 = np.abs(S - Y64).sum(axis=0)
+        s2 = (w * (S - mid)).sum(axis=0)
+        crps = s1 / K - s2 / (float(K) * float(K - 1 if fair else K))
+        crps = np.where(bad | np.isinf(X64).any(axis=0), np.nan, crps)
+        pit = np.where(bad, np.nan, ((X64 < Y64).sum(axis=0) + 0.5 * (X64 == Y64).sum(axis=0)) / K)
+        q = pin = None
+        if probs is not None:
+            p = np.asarray(list(probs), dtype=np.float64)
+            q = np.quantile(X64, p, axis=0).reshape((len(p),) + X64.shape[1:])
+            q = np.where(nan, np.nan, q)
+            pw = p.reshape((len(p),) + (1,) * (X64.ndim - 1))
+            pin = f(np.where(bad, np.nan, (Y64 - q) * (pw - (Y64 < q))))
+            q = f(q)
+        return SampleScores(f(crps), f(pit), q, pin)
+
+
+def targets_on_host(Y):
+    """the observed targets as float32 numpy, for the host route"""
+    if isinstance(Y, torch.Tensor):
+        Y = Y.detach().cpu().numpy()
+    return np.asarray(Y, dtype=np.float32)
+
+
+def targets_on_device(Y, device):
+    """the observed targets as a contiguous float32 tensor on `device` (a tensor already there is not copied)"""
+    if not isinstance(Y, torch.Tensor):
+        Y = torch.from_numpy(np.ascontiguousarray(np.asarray(Y, dtype=np.float32)))
+    return Y.detach().to(device=device, dtype=torch.float32).contiguous()
+
+
+class ScoreSink:
+    """the scores path of both run() functions: the device outputs, and pfp_scores on one row chunk's transposed draws"""
+
+    def __init__(self, Y, n, d, K, probs, fair, device):
+        self.Y = targets_on_device(Y, device)
+        if tuple(self.Y.shape) != (n, d):
+            raise ValueError("Y must have shape (%d, %d) (one target per condition row and column), got %s"
+                             % (n, d, tuple(self.Y.shape)))
+        f32 = dict(dtype=torch.float32, device=device)
+        self.n, self.d, self.K, self.fair = n, d, K, bool(fair)
+        self.crps, self.pit = torch.empty((n, d), **f32), torch.empty((n, d), **f32)
+        self.probs = self.q = self.pinball = None
+        if probs is not None:
+            self.probs = torch.tensor(probs, dtype=torch.float64, device=device)
+            self.q, self.pinball = torch.empty((len(probs), n, d), **f32), torch.empty((len(probs), n, d), **f32)
+
+    def chunk(self, pl, xt, lo, m):
+        """scores of rows lo .. lo + m"""
+        q, pb = self.q, self.pinball
+        part = q is not None and m != self.n                      # [Q, m, d] of [Q, n, d] is not contiguous
+        if part:
+            q, pb = (torch.empty((q.shape[0], m, self.d), dtype=torch.float32, device=q.device) for _ in range(2))
+        pl.scores(xt, self.Y[lo:lo + m], m, self.d, self.K, self.fair, self.probs, self.crps[lo:lo + m],
+                  self.pit[lo:lo + m], q, pb)
+        if part:
+            self.q[:, lo:lo + m].copy_(q)
+            self.pinball[:, lo:lo + m].copy_(pb)
+
+    def result(self):
+        return SampleScores(self.crps, self.pit, self.q, self.pinball)
+
+
 def _conditions(nf, C, eng):
     if type(C) == type(1):            # python int only, as nflow.py:135
         return C, None
@@ -103,8 +203,10 @@ def _host_draws(n, d, dev):
     return "device" if (n * d >= 16 and HostStreamOnDevice.usable(dev)) else "host"
 
 
-def run(nf, C, K, probs, ddof, want_stats, want_draws):
-    """-> (SampleStats of device tensors or None, draws [K, n, d] device tensor or None).  The caller has checked route()."""
+def run(nf, C, K, probs, ddof, want_stats, want_draws, scores=None):
+    """-> (SampleStats of device tensors or None, draws [K, n, d] device tensor or None).  The caller has checked route().
+    scores = (Y, fair): the scores path -- neither statistics nor draws; only the transposed draws are kept, per row chunk,
+    and the first item returned is a SampleScores of device tensors."""
     from . import _predict_lib as pl
     from .nflow import HostStreamOnDevice
     eng = nf.engine()
@@ -118,7 +220,12 @@ def run(nf, C, K, probs, ddof, want_stats, want_draws):
     state = pl.new_state(n, d, dev) if want_stats else None
     q_out = torch.empty((len(probs), n, d), **f32) if (want_stats and probs is not None) else None
     probs_dev = torch.tensor(probs, dtype=torch.float64, device=dev) if q_out is not None else None
-    chunks = quantile_row_chunks(n, d, K, XT_CHUNK_BYTES) if q_out is not None else ([(0, n)] if n else [])
+    sink = None
+    if scores is not None:
+        assert not (want_stats or want_draws)
+        sink = ScoreSink(scores[0], n, d, K, probs, scores[1], dev)
+    want_xt = q_out is not None or sink is not None
+    chunks = quantile_row_chunks(n, d, K, XT_CHUNK_BYTES) if want_xt else ([(0, n)] if n else [])
     keep = []
 
     def rows_of(t, lo, m):
@@ -127,9 +234,11 @@ def run(nf, C, K, probs, ddof, want_stats, want_draws):
     if not host:
         seeds = [nf.prior.next_seed() for _ in range(K)]          # what K successive sample() calls consume
         for lo, m in chunks:
-            xt = torch.empty((m, d, K), **f32) if q_out is not None else None
+            xt = torch.empty((m, d, K), **f32) if want_xt else None
             keep.append(eng.predict_draw(rows_of(Cd, lo, m), m, lo, seeds, None, n, 0, K, K, rows_of(state, lo, m), x_out, xt))
-            if xt is not None:
+            if sink is not None:
+                sink.chunk(pl, xt, lo, m)
+            elif xt is not None:
                 _chunk_quantiles(pl, xt, lo, m, d, K, probs_dev, q_out)
         torch.cuda.current_stream(dev).synchronize()             # the host seed arrays have been consumed
     elif n > 0:
@@ -140,7 +249,7 @@ def run(nf, C, K, probs, ddof, want_stats, want_draws):
         for ci, (lo, m) in enumerate(chunks):
             if ci > 0:
                 torch.set_rng_state(start)                        # every row chunk walks the same K draws of randn(n, d)
-            xt = torch.empty((m, d, K), **f32) if q_out is not None else None
+            xt = torch.empty((m, d, K), **f32) if want_xt else None
             hs = HostStreamOnDevice(dev).begin() if how == "device" else None
             try:
                 for k_lo, k_cnt in windows:
@@ -158,7 +267,9 @@ def run(nf, C, K, probs, ddof, want_stats, want_draws):
             finally:
                 if hs is not None:
                     hs.end()
-            if xt is not None:
+            if sink is not None:
+                sink.chunk(pl, xt, lo, m)
+            elif xt is not None:
                 _chunk_quantiles(pl, xt, lo, m, d, K, probs_dev, q_out)
     stats = None
     if want_stats:
@@ -167,6 +278,8 @@ def run(nf, C, K, probs, ddof, want_stats, want_draws):
             pl.finalize(state, n, d, ddof, mean, std, mn, mx)
         stats = SampleStats(mean, std, mn, mx, q_out)
     del keep
+    if sink is not None:
+        return sink.result(), None
     return stats, x_out
 
 

@@ -32,6 +32,7 @@ _SIGNATURES = {
                                       _VP, _SZ]),
     "pfp_finalize": (C.c_int, [_VP, _VP, _I64, _I32, _I32, _VP, _VP, _VP, _VP]),
     "pfp_quantiles": (C.c_int, [_VP, _VP, _I64, _I32, _I64, _VP, _I32, _VP]),
+    "pfp_scores": (C.c_int, [_VP, _VP, _VP, _I64, _I32, _I64, _I32, _VP, _I32, _VP, _VP, _VP, _VP]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -64,7 +65,10 @@ def lib():
                     raise PredictLibraryMissing("%s reports pfp_version() = %d, this binding is written for %d: rebuild it "
                                                 "(`make -C probaforms_amd/models/predict_csrc`)" % (LIB_PATH, have, ABI_VERSION))
                 for name, (res, args) in _SIGNATURES.items():
-                    fn = getattr(L, name)
+                    fn = getattr(L, name, None)
+                    if fn is None:                 # same ABI version, built before this entry point was added
+                        raise PredictLibraryMissing("%s has no %s: rebuild it (`make -C probaforms_amd/models/predict_csrc`)"
+                                                    % (LIB_PATH, name))
                     fn.restype, fn.argtypes = res, args
                 _lib = L
     return _lib
@@ -141,3 +145,13 @@ def quantiles(xt, n_rows, d, k_total, probs, q_out):
     """probs: float64 device tensor [Q]; q_out: float32 [Q, n_rows, d]"""
     check(lib().pfp_quantiles(_stream(), _f32(xt, "xt"), int(n_rows), int(d), int(k_total),
                               _ptr(probs, torch.float64, "probs"), int(probs.numel()), _f32(q_out, "q_out")), "pfp_quantiles")
+
+
+def scores(xt, y, n_rows, d, k_total, fair, probs, crps, pit, q_out, pinball):
+    """xt [n_rows, d, k_total], y [n_rows, d] float32; probs: float64 device tensor [Q] or None; crps, pit [n_rows, d] and
+    q_out, pinball [Q, n_rows, d] float32, each nullable"""
+    py, px = _f32(y, "y"), _f32(xt, "xt")
+    nq = 0 if probs is None else int(probs.numel())
+    check(lib().pfp_scores(_stream(), px, py, int(n_rows), int(d), int(k_total), int(bool(fair)),
+                           _ptr(probs, torch.float64, "probs", True) if nq else None, nq, _f32(crps, "crps", True),
+                           _f32(pit, "pit", True), _f32(q_out, "q_out", True), _f32(pinball, "pinball", True)), "pfp_scores")

@@ -215,3 +215,13 @@ class ConditionalNormal(GenModel):
         ``n_draws < 1``, a probability outside [0, 1] or quantiles with ``n_draws > 8192`` raise ValueError."""
         from . import _gendraw
         return _gendraw.sample_stats(self, C, n_draws, quantiles, ddof)
+
+    def sample_scores(self, C, Y, n_draws=1000, quantiles=(0.05, 0.95), fair=False):
+        """Scores of the predictive draws against the observed targets ``Y`` [n, d], as ``RealNVP.sample_scores``:
+        ``SampleScores(crps, pit, quantiles, pinball)`` of float32 numpy arrays [n, d] (quantiles and pinball [Q, n, d], or
+        None).  The eps draws come from torch's global CPU generator exactly as ``n_draws`` successive ``sample(C)`` calls
+        draw them, so a seeded call scores bitwise the draws a seeded ``sample_many`` returns; the draws, the sort and
+        the scores run on the device.  ``n_draws < 1``, ``n_draws > 8192``, a probability outside [0, 1] or a ``Y`` whose
+        shape is not (n, d) raise ValueError."""
+        from . import _gendraw
+        return _gendraw.sample_scores(self, C, Y, n_draws, quantiles, fair)

@@ -370,6 +370,25 @@ class NormalizingFlow(nn.Module):
                 return _predict.SampleStats(*(None if a is None else torch.from_numpy(a).to(DEVICE) for a in s))
             return _predict.run(self, C, K, probs, int(ddof), True, False)[0]
 
+    def sample_scores(self, C, Y, n_draws=1000, quantiles=(0.05, 0.95), fair=False):
+        """Per condition row and column, the scores of ``n_draws`` samples against the observed targets ``Y`` [n, var_size]:
+        ``SampleScores(crps, pit, quantiles, pinball)`` of float32 device tensors [n, var_size] (quantiles and pinball:
+        [Q, n, var_size], or None).  crps = mean |x - y| - mean |x - x'| / 2 over the draws (``fair=True``: the pair mean
+        over the K (K - 1) distinct pairs); pit = the mid-rank of y among the draws, in [0, 1]; quantiles as
+        ``sample_stats``; pinball = (y - Q) (p - [y < Q]).  The draws are those of ``sample_many``, sorted and scored on the
+        device in float64 with one rounding.  Consumes torch's global CPU generator exactly as the loop of ``sample(C)``
+        calls does.  ``n_draws < 1``, ``n_draws > 8192``, a probability outside [0, 1] or a ``Y`` whose shape is not
+        (n, var_size) raise ValueError.  A layer-wise flow, a user-assigned prior and a shape the kernel does not hold in LDS
+        fall back to that loop on the host (``sample`` n_draws times plus numpy)."""
+        from . import _predict
+        K, probs = _predict.validate_scores(n_draws, quantiles)
+        with torch.no_grad():
+            if self._predict_route() != "kernel":
+                X = _predict.loop_draws(lambda c: torch.as_tensor(self.sample(c)).detach().cpu().numpy(), C, K)
+                s = _predict.scores_of_draws(X, _predict.targets_on_host(Y), probs, fair)
+                return _predict.SampleScores(*(None if a is None else torch.from_numpy(a).to(DEVICE) for a in s))
+            return _predict.run(self, C, K, probs, 0, False, False, scores=(Y, fair))[0]
+
     # -- host staging (SURVEY.md 8(f) rank 3) -------------------------------------------------
     # one chunk of output rows: at least PIPELINE_CHUNK_BYTES and at least PIPELINE_MIN_ROWS rows (a launch of fewer
     # rows leaves CUs idle: 256 rows per workgroup).  Measured at API level, C2 sample(1M): 8 MB chunks 3.1 ms (device

@@ -8,6 +8,7 @@
  *   pfp_draw_accumulate   K draws per row through the inverse flow; running moments, the draws, their transpose
  *   pfp_finalize          running moments -> mean, std, min, max
  *   pfp_quantiles         exact quantiles (numpy's default 'linear') of the transposed draws
+ *   pfp_scores            CRPS, PIT, quantiles and pinball losses of the transposed draws against observed targets
  *
  * Conventions (as pf_cnormal.h)
  *   - every array is a DEVICE pointer unless it says HOST; sizes are plain integers;
@@ -45,7 +46,7 @@ extern "C" {
 
 #define PFP_VERSION 101         /* pfp_version(): bumped whenever an argument list or the state's layout or meaning changes */
 
-#define PFP_MAX_QUANTILE_DRAWS 8192   /* pfp_quantiles sorts one (row, column) series inside one workgroup's LDS */
+#define PFP_MAX_QUANTILE_DRAWS 8192   /* pfp_quantiles / pfp_scores sort one (row, column) series inside one workgroup's LDS */
 
 /*
  * Running moments of one (row, column): PFP_STATE_BYTES bytes, all zero = nothing seen yet.
@@ -105,6 +106,26 @@ int pfp_finalize(void *stream, const void *state, int64_t n_rows, int32_t d, int
  */
 int pfp_quantiles(void *stream, const float *xt, int64_t n_rows, int32_t d, int64_t k_total,
                   const double *probs, int32_t n_probs, float *q_out);
+
+/*
+ * Scores of every (row, column) series x_1 .. x_K = xt[r][j][:] against its observed target y[r][j], in float64 on the
+ * sorted series with one rounding to float32 (D = K, or K - 1 when fair != 0):
+ *   crps[r][j]       = 1/K sum_k |x_k - y|  -  1/(2 K D) sum_k sum_l |x_k - x_l|      (fair and K = 1: NaN, 0 / 0)
+ *   pit[r][j]        = (#{x_k < y} + 0.5 #{x_k == y}) / K                             (float comparisons: -0 == +0)
+ *   q_out[i][r][j]   = what pfp_quantiles returns for the same series and probs[i], bitwise
+ *   pinball[i][r][j] = (y - Q_i) (probs[i] - [y < Q_i]),  Q_i the float64 quantile before its rounding
+ * xt [n_rows, d, k_total] and y [n_rows, d] are not modified; crps, pit [n_rows, d] and q_out, pinball
+ * [n_probs, n_rows, d] are each nullable; probs [n_probs] float64 in [0, 1], NULL iff n_probs == 0;
+ * 1 <= k_total <= PFP_MAX_QUANTILE_DRAWS.  The pair sum is evaluated as 2 sum_i (2 i - K + 1) x_(i) over the sorted series,
+ * the sums in an order fixed by k_total alone (no atomics): a series' results are bitwise the same in any call.
+ * Non-finite values: a NaN in the series or in y makes crps, pit and every pinball of that (row, column) NaN (q_out
+ * only for a NaN in the series); otherwise the outputs are what numpy gives for the definitions above, pair sum included:
+ * a series holding an infinity has crps NaN (inf - inf), y = +-inf with a finite series has crps +inf.  Nothing leaves its
+ * (row, column).
+ */
+int pfp_scores(void *stream, const float *xt, const float *y, int64_t n_rows, int32_t d, int64_t k_total,
+               int32_t fair, const double *probs, int32_t n_probs,
+               float *crps, float *pit, float *q_out, float *pinball);
 
 #ifdef __cplusplus
 }

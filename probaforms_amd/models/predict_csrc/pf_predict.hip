@@ -20,6 +20,9 @@
 //     the state is read once when the row is picked up and written once when it is done.
 // A draw's value depends on nothing but its own column of the image, and the order of the float64 sums is fixed by
 // (k_lo, k_cnt) alone: rows split over calls reproduce one call bit for bit.
+//
+// k_quantiles / k_scores: one 256-thread workgroup per (row, column) series of the transposed draws sorts it in LDS; quantiles,
+// and the CRPS / PIT / pinball scores against an observed target, are one pass over the sorted series (see the kernels).
 #include "../../csrc/rnvp_common.h"
 #include "../../csrc/rnvp_generic_net.h"
 #include "../../csrc/rnvp_prior.h"
@@ -300,6 +303,44 @@ __device__ __forceinline__ float val_of(uint32_t k) {
     return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
 
+// the workgroup's 256 threads load one series into `keys` (P = 2^ceil(log2 K) entries, the P - K pad keys are 0xffffffff,
+// at or above every float's key) and sort it ascending with a bitonic network; ends on a barrier
+__device__ __forceinline__ void sort_series(uint32_t *keys, const float *__restrict__ x, int K, int P, int tid) {
+    for (int i = tid; i < P; i += 256) keys[i] = i < K ? key_of(x[i]) : 0xffffffffu;
+    __syncthreads();
+    for (int k = 2; k <= P; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < P; i += 256) {
+                const int p = i ^ j;
+                if (p > i) {
+                    const uint32_t a = keys[i], b = keys[p];
+                    const bool asc = (i & k) == 0;
+                    if ((a > b) == asc) { keys[i] = b; keys[p] = a; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// numpy's 'linear' quantile of the sorted series in float64 (before its rounding): virtual index p (K - 1), then
+// _lerp(a, b, t)
+__device__ __forceinline__ double quantile_of(const uint32_t *keys, int K, double prob, bool has_nan) {
+    const double pos = prob * (double)(K - 1);
+    double fl = floor(pos);
+    if (fl < 0.0) fl = 0.0;
+    if (fl > (double)(K - 1)) fl = (double)(K - 1);
+    const int lo = (int)fl, hi = lo + 1 < K ? lo + 1 : K - 1;
+    const double t = pos - fl;
+    const double a = (double)val_of(keys[lo]), b = (double)val_of(keys[hi]);
+    const double diff = b - a;
+    double res = a + diff * t;
+    if (t >= 0.5) res = b - diff * (1.0 - t);
+    if (diff == 0.0) res = a;
+    if (has_nan) res = NAN;
+    return res;
+}
+
 // one workgroup per (row, column) series: bitonic sort of P = 2^ceil(log2 K) keys in LDS, the P - K pad keys are
 // 0xffffffff (at or above every float's key) and only indices below K are read afterwards.  NaNs sort to the two ends
 // (by sign), so a series holds one iff keys[0] or keys[K - 1] decodes to NaN: every quantile of it is then NaN, as
@@ -310,38 +351,80 @@ k_quantiles(const float *__restrict__ xt, int64_t n_series, int K, int P, const 
     extern __shared__ __attribute__((aligned(16))) uint32_t keys[];
     const int tid = threadIdx.x;
     for (int64_t sr = blockIdx.x; sr < n_series; sr += gridDim.x) {
-        for (int i = tid; i < P; i += 256) keys[i] = i < K ? key_of(xt[sr * K + i]) : 0xffffffffu;
-        __syncthreads();
-        for (int k = 2; k <= P; k <<= 1) {
-            for (int j = k >> 1; j > 0; j >>= 1) {
-                for (int i = tid; i < P; i += 256) {
-                    const int p = i ^ j;
-                    if (p > i) {
-                        const uint32_t a = keys[i], b = keys[p];
-                        const bool asc = (i & k) == 0;
-                        if ((a > b) == asc) { keys[i] = b; keys[p] = a; }
-                    }
-                }
-                __syncthreads();
-            }
-        }
+        sort_series(keys, xt + sr * K, K, P, tid);
         const float v_lo = val_of(keys[0]), v_hi = val_of(keys[K - 1]);
         const bool has_nan = v_lo != v_lo || v_hi != v_hi;
+        for (int i = tid; i < nq; i += 256)
+            q_out[(int64_t)i * n_series + sr] = (float)quantile_of(keys, K, probs[i], has_nan);
+        __syncthreads();
+    }
+}
+
+// k_scores: k_quantiles' layout (one workgroup per series, the same sort), then ONE pass over the sorted series x_(0..K-1)
+// against the series' target y:
+//   S1 = sum_i |x_(i) - y|                       (K times the CRPS' first term)
+//   S2 = sum_i (2 i - K + 1) (x_(i) - c)         (= 1/2 sum_k sum_l |x_k - x_l|: every pair counts its larger member with +,
+//                                                 its smaller with -; the weights sum to zero, so any shift c cancels.  c is
+//                                                 the middle order statistic x_(K/2): the terms are then bounded by K times the
+//                                                 series' RANGE, wherever y lies)
+//   lt, eq = #{x_(i) < y}, #{x_(i) == y}         (on the float values: -0 == +0 although their keys differ)
+// Thread t sums i = t, t + 256, ... in that order in float64; the 256 partials are combined by a halving tree in LDS (t += t +
+// s for s = 128 .. 1).  The order depends on K alone: no atomics, the same series gives the same bits in any grid.
+// Non-finite: a NaN in the series (it sorts to an end) or in y makes crps, pit and every pinball NaN; a series holding an
+// infinity has crps NaN (the pair sum's diagonal forms inf - inf); y = +-inf with a finite series gives S1 = inf, S2 finite.
+// LDS in front of the keys: two float64 and two count partials per thread
+constexpr size_t kScoreScratch = 256 * (2 * sizeof(double) + 2 * sizeof(uint32_t));
+
+__global__ void __launch_bounds__(256)
+k_scores(const float *__restrict__ xt, const float *__restrict__ y, int64_t n_series, int K, int P, int fair,
+         const double *__restrict__ probs, int nq, float *__restrict__ crps, float *__restrict__ pit,
+         float *__restrict__ q_out, float *__restrict__ pinball) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char score_lds[];
+    double *r1 = reinterpret_cast<double *>(score_lds), *r2 = r1 + 256;        // the reduction scratch, then the keys
+    uint32_t *rl = reinterpret_cast<uint32_t *>(r2 + 256), *re = rl + 256, *keys = re + 256;
+    const int tid = threadIdx.x;
+    for (int64_t sr = blockIdx.x; sr < n_series; sr += gridDim.x) {
+        sort_series(keys, xt + sr * K, K, P, tid);
+        const float v_lo = val_of(keys[0]), v_hi = val_of(keys[K - 1]);
+        const bool has_nan = v_lo != v_lo || v_hi != v_hi;
+        const bool has_inf = isinf(v_lo) || isinf(v_hi);
+        const float yf = y[sr];
+        const bool bad = has_nan || yf != yf;
+        if (crps || pit) {
+            const float cf = val_of(keys[K >> 1]);
+            const double yd = (double)yf, c = isfinite(cf) ? (double)cf : 0.0;
+            double s1 = 0.0, s2 = 0.0;
+            uint32_t lt = 0, eq = 0;
+            for (int i = tid; i < K; i += 256) {
+                const float v = val_of(keys[i]);
+                s1 += fabs((double)v - yd);
+                s2 += (double)(2 * i - K + 1) * ((double)v - c);
+                lt += v < yf ? 1u : 0u;
+                eq += v == yf ? 1u : 0u;
+            }
+            r1[tid] = s1; r2[tid] = s2; rl[tid] = lt; re[tid] = eq;
+            __syncthreads();
+            for (int s = 128; s > 0; s >>= 1) {
+                if (tid < s) { r1[tid] += r1[tid + s]; r2[tid] += r2[tid + s]; rl[tid] += rl[tid + s]; re[tid] += re[tid + s]; }
+                __syncthreads();
+            }
+            if (tid == 0) {
+                const double kd = (double)K, dd = fair ? kd - 1.0 : kd;
+                double cr = r1[0] / kd - r2[0] / (kd * dd);             // K = 1 and fair: 0 / 0
+                if (bad || has_inf) cr = NAN;
+                const double pt = bad ? (double)NAN : ((double)rl[0] + 0.5 * (double)re[0]) / kd;
+                if (crps) crps[sr] = (float)cr;
+                if (pit) pit[sr] = (float)pt;
+            }
+        }
         for (int i = tid; i < nq; i += 256) {
-            // numpy's 'linear': virtual index p (K - 1), then _lerp(a, b, t)
-            const double pos = probs[i] * (double)(K - 1);
-            double fl = floor(pos);
-            if (fl < 0.0) fl = 0.0;
-            if (fl > (double)(K - 1)) fl = (double)(K - 1);
-            const int lo = (int)fl, hi = lo + 1 < K ? lo + 1 : K - 1;
-            const double t = pos - fl;
-            const double a = (double)val_of(keys[lo]), b = (double)val_of(keys[hi]);
-            const double diff = b - a;
-            double res = a + diff * t;
-            if (t >= 0.5) res = b - diff * (1.0 - t);
-            if (diff == 0.0) res = a;
-            if (has_nan) res = NAN;
-            q_out[(int64_t)i * n_series + sr] = (float)res;
+            const double p = probs[i], q = quantile_of(keys, K, p, has_nan), yd = (double)yf;
+            if (q_out) q_out[(int64_t)i * n_series + sr] = (float)q;
+            if (pinball) {
+                double pb = (yd - q) * (p - (yd < q ? 1.0 : 0.0));
+                if (bad) pb = NAN;
+                pinball[(int64_t)i * n_series + sr] = (float)pb;
+            }
         }
         __syncthreads();
     }
@@ -459,6 +542,22 @@ int pfp_quantiles(void *stream, const float *xt, int64_t n_rows, int32_t d, int6
     const int grid = (int)(n_series < kMaxGrid ? n_series : kMaxGrid);
     hipLaunchKernelGGL(k_quantiles, dim3(grid), dim3(256), (size_t)P * sizeof(uint32_t), (hipStream_t)stream, xt, n_series,
                        (int)k_total, P, probs, (int)n_probs, q_out);
+    return (int)hipGetLastError();
+}
+
+int pfp_scores(void *stream, const float *xt, const float *y, int64_t n_rows, int32_t d, int64_t k_total,
+               int32_t fair, const double *probs, int32_t n_probs,
+               float *crps, float *pit, float *q_out, float *pinball) {
+    if (!xt || !y || n_rows < 0 || d < 1 || k_total < 1 || n_probs < 0 || (n_probs > 0 && !probs)) return PFP_EINVAL;
+    if (k_total > PFP_MAX_QUANTILE_DRAWS) return PFP_EUNSUPPORTED;
+    const int64_t n_series = n_rows * d;
+    if (n_series == 0) return PFP_OK;
+    int P = 1;
+    while (P < k_total) P <<= 1;
+    const int grid = (int)(n_series < kMaxGrid ? n_series : kMaxGrid);
+    hipLaunchKernelGGL(k_scores, dim3(grid), dim3(256), kScoreScratch + (size_t)P * sizeof(uint32_t), (hipStream_t)stream, xt, y,
+                       n_series, (int)k_total, P, (int)(fair != 0), n_probs > 0 ? probs : nullptr, (int)n_probs, crps, pit, q_out,
+                       pinball);
     return (int)hipGetLastError();
 }
 

@@ -310,6 +310,31 @@ class RealNVP(GenModel):
         s = self.nf.sample_stats(C, K, probs, int(ddof))
         return _predict.SampleStats(*(None if a is None else a.cpu().numpy() for a in s))
 
+    def sample_scores(self, C, Y, n_draws=1000, quantiles=(0.05, 0.95), fair=False):
+        """Scores of the predictive distribution of every condition row against what was observed (a name the reference does
+        not have): where docs/examples/regression.ipynb and forecast.ipynb stop at a plot of the 5 % / 95 % band over the
+        true series, this says whether the band is calibrated and how sharp it is.  ``Y`` [n, d] holds the observed targets
+        (numpy, array-like or a torch tensor; a tensor on the device stays there).  Returns ``SampleScores(crps, pit,
+        quantiles, pinball)``: float32 numpy arrays [n, d]; quantiles and pinball [Q, n, d] or None.  Per (row, column), over
+        the ``n_draws`` samples x_k: crps = mean |x_k - y| - mean |x_k - x_l| / 2 (``fair=True``: the pair mean over the
+        K (K - 1) distinct pairs; NaN for one draw); pit = (#{x_k < y} + #{x_k == y} / 2) / K, uniform on [0, 1] for a
+        calibrated model; quantiles as ``sample_stats`` (numpy's 'linear'); pinball = (y - Q) (p - [y < Q]).  float64
+        arithmetic on the sorted draws, one rounding.  A NaN among the draws or in y makes the scores of that (row, column)
+        NaN and touches no other.  ``C`` is an array or a python int, as in ``sample``.  Consumes torch's global CPU
+        generator exactly as the loop of ``sample(C)`` calls does, so a seeded call scores bitwise the draws a seeded
+        ``sample_many`` returns and leaves the generator where the loop leaves it.  ``n_draws < 1``, ``n_draws > 8192`` (the
+        draws are always sorted), a probability outside [0, 1] or a ``Y`` whose shape is not (n, d) raise ValueError.  A
+        layer-wise flow, a user-assigned prior and a shape the kernel does not hold in LDS fall back to the loop on the host
+        (``self.sample`` n_draws times plus numpy), so the call always works."""
+        from . import _predict
+        K, probs = _predict.validate_scores(n_draws, quantiles)
+        if self.nf._predict_route() != "kernel":
+            return _predict.scores_of_draws(_predict.loop_draws(self.sample, C, K), _predict.targets_on_host(Y), probs, fair)
+        if type(C) != type(1):
+            C = _to_device_f32(C, self.nf.engine().device)
+        s = self.nf.sample_scores(C, Y, K, probs, fair)
+        return _predict.SampleScores(*(None if a is None else a.cpu().numpy() for a in s))
+
     def _sample_sharded(self, C, n, rank, world, gather):
         import torch.distributed as dist
         eng = self.nf.engine()
