@@ -7,9 +7,10 @@ device memory and streams (tensor.data_ptr(), torch.cuda.current_stream()).
 """
 import ctypes as C
 import os
-import threading
 
 import torch
+
+from ._cbind import Library, LibraryMissing, ptr, stream as _stream
 
 MAX_HIDDEN = 8
 ABI_VERSION = 600          # rnvp_version() of the library this binding matches (include/rnvp_hip.h RNVP_HIP_VERSION)
@@ -108,12 +109,9 @@ class CvaeShape(C.Structure):
         return s
 
 
-class HipLibraryMissing(RuntimeError):
+class HipLibraryMissing(LibraryMissing):
     pass
 
-
-_lib = None
-_lock = threading.Lock()
 
 _VP, _I64, _U64, _F, _D, _SZ = C.c_void_p, C.c_int64, C.c_uint64, C.c_float, C.c_double, C.c_size_t
 _SP = C.POINTER(RnvpShape)
@@ -176,52 +174,14 @@ _SIGNATURES = {
 EXPORTS = tuple(_SIGNATURES)
 
 
-def lib():
-    """Load librnvp_hip.so once; raise loudly if it has not been built."""
-    global _lib
-    if _lib is None:
-        with _lock:
-            if _lib is None:
-                if not os.path.exists(LIB_PATH):
-                    raise HipLibraryMissing(
-                        "%s not found: build it with `make -C probaforms_amd/csrc` "
-                        "(or `python -c 'import __graft_entry__ as g; g.build()'`). "
-                        "probaforms_amd has no CPU fallback." % LIB_PATH)
-                L = C.CDLL(LIB_PATH)
-                L.rnvp_version.restype, L.rnvp_version.argtypes = C.c_int, []
-                have = int(L.rnvp_version())
-                if have != ABI_VERSION:
-                    # an older / newer build of the same library (RNVP_HIP_LIB, a stale A/B variant): struct layouts and
-                    # argument lists differ between versions, calling through would corrupt memory silently
-                    raise HipLibraryMissing("%s reports rnvp_version() = %d, this binding is written for %d: rebuild it "
-                                            "(`make -C probaforms_amd/csrc`)" % (LIB_PATH, have, ABI_VERSION))
-                for name, (res, args) in _SIGNATURES.items():
-                    fn = getattr(L, name)
-                    fn.restype, fn.argtypes = res, args
-                _lib = L
-    return _lib
-
-
-def check(status, what):
-    if status != 0:
-        msg = lib().rnvp_status_string(status)
-        raise RuntimeError("%s failed: %s (status %d)" % (what, msg.decode() if msg else "?", status))
+LIBRARY = Library(LIB_PATH, os.path.join(_HERE, "csrc"), "rnvp_", ABI_VERSION, _SIGNATURES, HipLibraryMissing,
+                  "probaforms_amd has no CPU fallback.")
+lib = LIBRARY.load
+check = LIBRARY.check
 
 
 def _ptr(t, dtype, what):
-    if t is None:
-        return None
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError("%s must be a tensor on a HIP device (got %s); probaforms_amd has no CPU path"
-                           % (what, getattr(t, "device", type(t))))
-    if t.dtype != dtype or not t.is_contiguous():
-        raise RuntimeError("%s must be contiguous %s (got %s, contiguous=%s)"
-                           % (what, dtype, t.dtype, t.is_contiguous()))
-    return t.data_ptr()
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
+    return ptr(t, dtype, what, True, "; probaforms_amd has no CPU path")
 
 
 def _call(name, args):

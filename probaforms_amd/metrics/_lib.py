@@ -6,9 +6,10 @@ missing library or a tensor off the HIP device raises.
 """
 import ctypes as C
 import os
-import threading
 
 import torch
+
+from .._cbind import Library, LibraryMissing, ptr as _ptr
 
 ABI_VERSION = 101          # pfm_version() of the library this binding matches (pf_metrics.h PFM_VERSION)
 MOMENTS_MAX_D = 4096       # PFM_MOMENTS_MAX_D
@@ -35,50 +36,15 @@ _SIGNATURES = {
 }
 EXPORTS = tuple(_SIGNATURES)
 
-_lib = None
-_lock = threading.Lock()
 
-
-class MetricsLibraryMissing(RuntimeError):
+class MetricsLibraryMissing(LibraryMissing):
     pass
 
 
-def lib():
-    """Load libpf_metrics.so once; raise loudly if it has not been built or is another ABI version."""
-    global _lib
-    if _lib is None:
-        with _lock:
-            if _lib is None:
-                if not os.path.exists(LIB_PATH):
-                    raise MetricsLibraryMissing(
-                        "%s not found: build it with `make -C probaforms_amd/metrics/csrc` "
-                        "(or `python -c 'import __graft_entry__ as g; g.build()'`). "
-                        "probaforms_amd.metrics has no CPU fallback." % LIB_PATH)
-                L = C.CDLL(LIB_PATH)
-                L.pfm_version.restype, L.pfm_version.argtypes = C.c_int, []
-                have = int(L.pfm_version())
-                if have != ABI_VERSION:
-                    raise MetricsLibraryMissing("%s reports pfm_version() = %d, this binding is written for %d: rebuild it "
-                                                "(`make -C probaforms_amd/metrics/csrc`)" % (LIB_PATH, have, ABI_VERSION))
-                for name, (res, args) in _SIGNATURES.items():
-                    fn = getattr(L, name)
-                    fn.restype, fn.argtypes = res, args
-                _lib = L
-    return _lib
-
-
-def check(status, what):
-    if status != 0:
-        msg = lib().pfm_status_string(status)
-        raise RuntimeError("%s failed: %s (status %d)" % (what, msg.decode() if msg else "?", status))
-
-
-def _ptr(t, dtype, what):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError("%s must be a tensor on a HIP device (got %s)" % (what, getattr(t, "device", type(t))))
-    if t.dtype != dtype or not t.is_contiguous():
-        raise RuntimeError("%s must be contiguous %s (got %s, contiguous=%s)" % (what, dtype, t.dtype, t.is_contiguous()))
-    return t.data_ptr()
+LIBRARY = Library(LIB_PATH, os.path.dirname(LIB_PATH), "pfm_", ABI_VERSION, _SIGNATURES, MetricsLibraryMissing,
+                  "probaforms_amd.metrics has no CPU fallback.")
+lib = LIBRARY.load
+check = LIBRARY.check
 
 
 def mmd_workspace_bytes(nx, ny, d, reps):

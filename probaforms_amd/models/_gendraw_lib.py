@@ -7,9 +7,10 @@ replaces (see models/_gendraw.py).
 """
 import ctypes as C
 import os
-import threading
 
 import torch
+
+from .._cbind import Library, LibraryMissing, f32 as _f32, ptr as _ptr, stream as _stream
 
 ABI_VERSION = 100                  # pfg_version() of the library this binding matches (pf_gendraw.h PFG_VERSION)
 EUNSUPPORTED = -2                  # PFG_EUNSUPPORTED
@@ -60,11 +61,8 @@ _SIGNATURES = {
 }
 EXPORTS = tuple(_SIGNATURES)
 
-_lib = None
-_lock = threading.Lock()
 
-
-class GendrawLibraryMissing(RuntimeError):
+class GendrawLibraryMissing(LibraryMissing):
     pass
 
 
@@ -72,55 +70,10 @@ class Unsupported(RuntimeError):
     """one draw tile's activations do not fit the LDS, or d > MAX_D (PFG_EUNSUPPORTED)"""
 
 
-def lib():
-    """Load libpf_gendraw.so once; raise loudly if it has not been built or is another ABI version."""
-    global _lib
-    if _lib is None:
-        with _lock:
-            if _lib is None:
-                if not os.path.exists(LIB_PATH):
-                    raise GendrawLibraryMissing(
-                        "%s not found: build it with `make -C probaforms_amd/models/gendraw_csrc` "
-                        "(or `python -c 'import __graft_entry__ as g; g.build()'`)." % LIB_PATH)
-                L = C.CDLL(LIB_PATH)
-                L.pfg_version.restype, L.pfg_version.argtypes = C.c_int, []
-                have = int(L.pfg_version())
-                if have != ABI_VERSION:
-                    raise GendrawLibraryMissing("%s reports pfg_version() = %d, this binding is written for %d: rebuild it "
-                                                "(`make -C probaforms_amd/models/gendraw_csrc`)" % (LIB_PATH, have, ABI_VERSION))
-                for name, (res, args) in _SIGNATURES.items():
-                    fn = getattr(L, name)
-                    fn.restype, fn.argtypes = res, args
-                _lib = L
-    return _lib
-
-
-def check(status, what):
-    if status == EUNSUPPORTED:
-        raise Unsupported("%s: shape not supported" % what)
-    if status != 0:
-        msg = lib().pfg_status_string(status)
-        raise RuntimeError("%s failed: %s (status %d)" % (what, msg.decode() if msg else "?", status))
-
-
-def _ptr(t, dtype, what, nullable=False):
-    if t is None:
-        if nullable:
-            return None
-        raise RuntimeError("%s is required" % what)
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError("%s must be a tensor on a HIP device (got %s)" % (what, getattr(t, "device", type(t))))
-    if t.dtype != dtype or not t.is_contiguous():
-        raise RuntimeError("%s must be contiguous %s (got %s, contiguous=%s)" % (what, dtype, t.dtype, t.is_contiguous()))
-    return t.data_ptr()
-
-
-def _f32(t, what, nullable=False):
-    return _ptr(t, torch.float32, what, nullable)
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
+LIBRARY = Library(LIB_PATH, os.path.dirname(LIB_PATH), "pfg_", ABI_VERSION, _SIGNATURES, GendrawLibraryMissing,
+                  unsupported=(EUNSUPPORTED, Unsupported))
+lib = LIBRARY.load
+check = LIBRARY.check
 
 
 def workspace_bytes(net, k_cnt):

@@ -7,11 +7,11 @@ replaces (see NormalizingFlow.sample_stats).
 """
 import ctypes as C
 import os
-import threading
 
 import numpy as np
 import torch
 
+from .._cbind import Library, LibraryMissing, f32 as _f32, ptr as _ptr, stream as _stream
 from .._hip import RnvpShape
 
 ABI_VERSION = 101                  # pfp_version() of the library this binding matches (pf_predict.h PFP_VERSION)
@@ -36,11 +36,8 @@ _SIGNATURES = {
 }
 EXPORTS = tuple(_SIGNATURES)
 
-_lib = None
-_lock = threading.Lock()
 
-
-class PredictLibraryMissing(RuntimeError):
+class PredictLibraryMissing(LibraryMissing):
     pass
 
 
@@ -48,58 +45,10 @@ class Unsupported(RuntimeError):
     """the shape's per-tile image does not fit the LDS (PFP_EUNSUPPORTED)"""
 
 
-def lib():
-    """Load libpf_predict.so once; raise loudly if it has not been built or is another ABI version."""
-    global _lib
-    if _lib is None:
-        with _lock:
-            if _lib is None:
-                if not os.path.exists(LIB_PATH):
-                    raise PredictLibraryMissing(
-                        "%s not found: build it with `make -C probaforms_amd/models/predict_csrc` "
-                        "(or `python -c 'import __graft_entry__ as g; g.build()'`)." % LIB_PATH)
-                L = C.CDLL(LIB_PATH)
-                L.pfp_version.restype, L.pfp_version.argtypes = C.c_int, []
-                have = int(L.pfp_version())
-                if have != ABI_VERSION:
-                    raise PredictLibraryMissing("%s reports pfp_version() = %d, this binding is written for %d: rebuild it "
-                                                "(`make -C probaforms_amd/models/predict_csrc`)" % (LIB_PATH, have, ABI_VERSION))
-                for name, (res, args) in _SIGNATURES.items():
-                    fn = getattr(L, name, None)
-                    if fn is None:                 # same ABI version, built before this entry point was added
-                        raise PredictLibraryMissing("%s has no %s: rebuild it (`make -C probaforms_amd/models/predict_csrc`)"
-                                                    % (LIB_PATH, name))
-                    fn.restype, fn.argtypes = res, args
-                _lib = L
-    return _lib
-
-
-def check(status, what):
-    if status == EUNSUPPORTED:
-        raise Unsupported("%s: shape not supported" % what)
-    if status != 0:
-        msg = lib().pfp_status_string(status)
-        raise RuntimeError("%s failed: %s (status %d)" % (what, msg.decode() if msg else "?", status))
-
-
-def _ptr(t, dtype, what, nullable=False):
-    if t is None:
-        if nullable:
-            return None
-        raise RuntimeError("%s is required" % what)
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError("%s must be a tensor on a HIP device (got %s)" % (what, getattr(t, "device", type(t))))
-    if t.dtype != dtype or not t.is_contiguous():
-        raise RuntimeError("%s must be contiguous %s (got %s, contiguous=%s)" % (what, dtype, t.dtype, t.is_contiguous()))
-    return t.data_ptr()
-
-
-def _f32(t, what, nullable=False):
-    return _ptr(t, torch.float32, what, nullable)
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
+LIBRARY = Library(LIB_PATH, os.path.dirname(LIB_PATH), "pfp_", ABI_VERSION, _SIGNATURES, PredictLibraryMissing,
+                  unsupported=(EUNSUPPORTED, Unsupported))
+lib = LIBRARY.load
+check = LIBRARY.check
 
 
 def workspace_bytes(shape, k_cnt):

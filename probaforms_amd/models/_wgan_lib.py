@@ -6,9 +6,10 @@ kernels do not support or a tensor off the HIP device raises.
 """
 import ctypes as C
 import os
-import threading
 
 import torch
+
+from .._cbind import Library, LibraryMissing, f32 as _f32, ptr as _ptr, stream as _stream
 
 ABI_VERSION = 101          # pfw_version() of the library this binding matches (pf_wgan.h PFW_VERSION)
 MAX_HIDDEN = 8             # PFW_MAX_HIDDEN
@@ -76,62 +77,15 @@ _SIGNATURES = {
 }
 EXPORTS = tuple(_SIGNATURES)
 
-_lib = None
-_lock = threading.Lock()
 
-
-class WganLibraryMissing(RuntimeError):
+class WganLibraryMissing(LibraryMissing):
     pass
 
 
-def lib():
-    """Load libpf_wgan.so once; raise loudly if it has not been built or is another ABI version."""
-    global _lib
-    if _lib is None:
-        with _lock:
-            if _lib is None:
-                if not os.path.exists(LIB_PATH):
-                    raise WganLibraryMissing(
-                        "%s not found: build it with `make -C probaforms_amd/models/wgan_csrc` "
-                        "(or `python -c 'import __graft_entry__ as g; g.build()'`). "
-                        "ConditionalWGAN has no CPU fallback." % LIB_PATH)
-                L = C.CDLL(LIB_PATH)
-                L.pfw_version.restype, L.pfw_version.argtypes = C.c_int, []
-                have = int(L.pfw_version())
-                if have != ABI_VERSION:
-                    raise WganLibraryMissing("%s reports pfw_version() = %d, this binding is written for %d: rebuild it "
-                                             "(`make -C probaforms_amd/models/wgan_csrc`)" % (LIB_PATH, have, ABI_VERSION))
-                for name, (res, args) in _SIGNATURES.items():
-                    fn = getattr(L, name)
-                    fn.restype, fn.argtypes = res, args
-                _lib = L
-    return _lib
-
-
-def check(status, what):
-    if status != 0:
-        msg = lib().pfw_status_string(status)
-        raise RuntimeError("%s failed: %s (status %d)" % (what, msg.decode() if msg else "?", status))
-
-
-def _ptr(t, dtype, what, nullable=False):
-    if t is None:
-        if nullable:
-            return None
-        raise RuntimeError("%s is required" % what)
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError("%s must be a tensor on a HIP device (got %s)" % (what, getattr(t, "device", type(t))))
-    if t.dtype != dtype or not t.is_contiguous():
-        raise RuntimeError("%s must be contiguous %s (got %s, contiguous=%s)" % (what, dtype, t.dtype, t.is_contiguous()))
-    return t.data_ptr()
-
-
-def _f32(t, what, nullable=False):
-    return _ptr(t, torch.float32, what, nullable)
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
+LIBRARY = Library(LIB_PATH, os.path.dirname(LIB_PATH), "pfw_", ABI_VERSION, _SIGNATURES, WganLibraryMissing,
+                  "ConditionalWGAN has no CPU fallback.")
+lib = LIBRARY.load
+check = LIBRARY.check
 
 
 def param_count(shape, net):

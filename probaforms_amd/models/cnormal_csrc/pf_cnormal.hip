@@ -18,17 +18,19 @@
 // No float atomics anywhere: a call is bitwise reproducible, and pfn_fit_epoch is the same launches as the loop of
 // pfn_train_step calls.
 #include "../../csrc/rnvp_common.h"
+#include "../pf_rowtile.h"
 
 #include <math.h>
 
 #include "pf_cnormal.h"
 
+using pf_rowtile::big_lds;
+using pf_rowtile::kLds;
+using pf_rowtile::Plan;
+
 namespace {
 
 constexpr int NT = 256;                   // threads of every workgroup here
-constexpr size_t kLds = 160 * 1024;       // LDS of one CU on gfx950
-constexpr int kTargetWg = 256;            // k_step aims at one workgroup per CU
-constexpr int kMinTile = 8;               // ... with at least 8 batch rows per workgroup
 constexpr int kInvPer = (2 * PFN_MAX_D * PFN_MAX_D + NT - 1) / NT;   // elements of the [d, 2d] system per thread
 
 struct NShape {
@@ -87,47 +89,13 @@ int tile_cap(const NShape &w, int unit) {
     return (int)(R > NT ? NT : (R < 0 ? 0 : R));
 }
 
-// rows per k_step workgroup for a batch of `rows`: at least kMinTile (latency: more workgroups only add partials), enough
-// that ~kTargetWg workgroups cover the batch, at most what LDS holds
-int step_tile(const NShape &w, int64_t rows) {
-    const int cap = tile_cap(w, w.step_unit);
-    int R = kMinTile;
-    while ((int64_t)R * kTargetWg < rows) R *= 2;
-    return R < cap ? R : cap;
-}
-
-int64_t step_wg_bound(const NShape &w, int64_t batch_rows) {
-    const int cap = tile_cap(w, w.step_unit);
-    if (cap < 1) return 0;
-    const int lo = cap < kMinTile ? cap : kMinTile;
-    const int64_t a = (batch_rows + lo - 1) / lo;
-    int64_t b = (batch_rows + cap - 1) / cap;
-    if (b < kTargetWg) b = kTargetWg;
-    return a < b ? a : b;
-}
-
-// what one launch is made of: rows per workgroup, LDS bytes, workgroups.  enqueue_step / pfn_forward launch from these and
-// pfn_tiling reports them; tile == 0: the shape does not fit
-struct Plan {
-    int tile;
-    size_t lds;
-    int64_t wgs;
-};
-
+// the launches (pf_rowtile::Plan): enqueue_step / pfn_forward launch from these and pfn_tiling reports them
 Plan step_plan(const NShape &w, int64_t rows) {
-    Plan p{step_tile(w, rows), 0, 0};
-    if (p.tile < 1) return Plan{0, 0, 0};
-    p.lds = (size_t)w.shared + (size_t)(p.tile + 1) * w.step_unit * sizeof(float);
-    p.wgs = (rows + p.tile - 1) / p.tile;
-    return p;
+    return pf_rowtile::make_plan(pf_rowtile::step_tile(tile_cap(w, w.step_unit), rows), w.shared, 1, w.step_unit, rows);
 }
 
 Plan fwd_plan(const NShape &w, int64_t n) {
-    Plan p{tile_cap(w, w.fwd_unit), 0, 0};
-    if (p.tile < 1) return Plan{0, 0, 0};
-    p.lds = (size_t)w.shared + (size_t)(p.tile + 1) * w.fwd_unit * sizeof(float);
-    p.wgs = (n + p.tile - 1) / p.tile;
-    return p;
+    return pf_rowtile::make_plan(tile_cap(w, w.fwd_unit), w.shared, 1, w.fwd_unit, n);
 }
 
 struct Ws {
@@ -138,7 +106,7 @@ struct Ws {
 };
 
 size_t ws_bytes(const NShape &w, int64_t batch_rows, Ws *out, void *base) {
-    const int64_t G = step_wg_bound(w, batch_rows);
+    const int64_t G = pf_rowtile::step_wg_bound(tile_cap(w, w.step_unit), batch_rows);
     const size_t a = rnvp::align_up((size_t)G * w.P * sizeof(float), 256);
     const size_t b = rnvp::align_up((size_t)G * sizeof(float), 256);
     const size_t c = rnvp::align_up((size_t)PFN_MAX_D * PFN_MAX_D * sizeof(float), 256);
@@ -539,12 +507,6 @@ __global__ __launch_bounds__(NT) void k_forward(NShape w, int T, const float *__
 
 std::atomic<uint64_t> g_lds_step{0}, g_lds_fwd{0};
 
-template <typename K>
-int big_lds(K kernel, size_t bytes, std::atomic<uint64_t> &done) {
-    if (bytes <= 64 * 1024) return PFN_OK;
-    return rnvp::allow_big_lds(reinterpret_cast<const void *>(kernel), (int)kLds, done);
-}
-
 int enqueue_step(hipStream_t st, const NShape &w, float *params, float *m, float *v, const float *x, const float *c,
                  const int64_t *ri, int64_t rows, const rnvp::AdamK *adam, float *grad_out, float *loss_out,
                  int32_t *status, int first, const Ws &ws) {
@@ -619,7 +581,7 @@ int pfn_tiling(const pfn_shape *s, int64_t rows, pfn_tiling_info *out) {
     if (out->step_cap < 1) return PFN_EUNSUPPORTED;
     const Plan st = step_plan(w, rows);
     out->step_tile = st.tile; out->step_wgs = st.wgs; out->step_lds_bytes = (int64_t)st.lds;
-    out->step_wg_bound = step_wg_bound(w, rows);
+    out->step_wg_bound = pf_rowtile::step_wg_bound(out->step_cap, rows);
     return PFN_OK;
 }
 

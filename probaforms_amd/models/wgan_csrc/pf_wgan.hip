@@ -20,20 +20,21 @@
 // No float atomics anywhere: a call is bitwise reproducible, and pfw_fit_epoch is the same launches as the loop of
 // pfw_train_step calls.
 #include "../../csrc/rnvp_generic_net.h"
+#include "../pf_rowtile.h"
 
 #include <math.h>
 
 #include "pf_wgan.h"
 
 using rnvp::KShape;
+using pf_rowtile::big_lds;
+using pf_rowtile::kLds;
+using pf_rowtile::Plan;
 
 namespace {
 
 constexpr int NT = 256;                   // threads of a k_step workgroup (the parameter sweeps use all of them)
 constexpr int FWD_T = 64;                 // rows of an inference / epoch-loss tile (one wave)
-constexpr size_t kLds = 160 * 1024;       // LDS of one CU on gfx950
-constexpr int kTargetWg = 256;            // k_step aims at one workgroup per CU
-constexpr int kMinTile = 8;               // ... with at least 8 batch rows per workgroup
 constexpr int kFinishT = 256;
 
 // the nets of one shape, as rnvp::KShape (L = 1; KShape::d = leading input columns whose gradient the backward produces)
@@ -98,25 +99,6 @@ int step_tile_cap(const WShape &w) {
     return (int)(R < 0 ? 0 : R);
 }
 
-// rows per k_step workgroup for a batch of `rows`: at least kMinTile (latency: more workgroups only add partials), enough
-// that ~kTargetWg workgroups cover the batch, at most what LDS holds
-int step_tile(const WShape &w, int64_t rows) {
-    const int cap = step_tile_cap(w);
-    int R = kMinTile;
-    while ((int64_t)R * kTargetWg < rows) R *= 2;
-    return R < cap ? R : cap;
-}
-
-int64_t step_wg_bound(const WShape &w, int64_t batch_rows) {
-    const int cap = step_tile_cap(w);
-    if (cap < 1) return 0;
-    const int lo = cap < kMinTile ? cap : kMinTile;
-    const int64_t a = (batch_rows + lo - 1) / lo;
-    int64_t b = (batch_rows + cap - 1) / cap;
-    if (b < kTargetWg) b = kTargetWg;
-    return a < b ? a : b;
-}
-
 // rows of an epoch-loss tile (2T + 1 LDS rows) / of an inference tile (T + 1 LDS rows)
 int eloss_tile(const WShape &w) {
     int64_t S = (int64_t)(kLds / ((size_t)w.fwd_unit * sizeof(float)));
@@ -132,38 +114,15 @@ int fwd_tile(int unit) {
     return (int)(T > FWD_T ? FWD_T : (T < 0 ? 0 : T));
 }
 
-// what one launch is made of: rows per workgroup, LDS bytes, workgroups.  enqueue_* / pfw_generate / pfw_critic launch from
-// these and pfw_tiling reports them; tile == 0: the shape does not fit
-struct Plan {
-    int tile;
-    size_t lds;
-    int64_t wgs;
-};
-
+// the launches (pf_rowtile::Plan): enqueue_* / pfw_generate / pfw_critic launch from these and pfw_tiling reports them
 Plan step_plan(const WShape &w, int64_t rows) {
-    Plan p{step_tile(w, rows), 0, 0};
-    if (p.tile < 1) return Plan{0, 0, 0};
-    p.lds = (size_t)(2 * p.tile + 1) * w.step_unit * sizeof(float);
-    p.wgs = (rows + p.tile - 1) / p.tile;
-    return p;
+    return pf_rowtile::make_plan(pf_rowtile::step_tile(step_tile_cap(w), rows), 0, 2, w.step_unit, rows);
 }
 
-Plan eloss_plan(const WShape &w, int64_t n) {
-    Plan p{eloss_tile(w), 0, 0};
-    if (p.tile < 1) return Plan{0, 0, 0};
-    p.lds = (size_t)(2 * p.tile + 1) * w.fwd_unit * sizeof(float);
-    p.wgs = (n + p.tile - 1) / p.tile;
-    return p;
-}
+Plan eloss_plan(const WShape &w, int64_t n) { return pf_rowtile::make_plan(eloss_tile(w), 0, 2, w.fwd_unit, n); }
 
 // pfw_generate (unit = gen_unit) / pfw_critic (unit = crit_unit)
-Plan fwd_plan(int unit, int64_t n) {
-    Plan p{fwd_tile(unit), 0, 0};
-    if (p.tile < 1) return Plan{0, 0, 0};
-    p.lds = (size_t)(p.tile + 1) * unit * sizeof(float);
-    p.wgs = (n + p.tile - 1) / p.tile;
-    return p;
-}
+Plan fwd_plan(int unit, int64_t n) { return pf_rowtile::make_plan(fwd_tile(unit), 0, 1, unit, n); }
 
 struct Ws {
     float *gpart;   // [G][PG + PD]
@@ -172,7 +131,7 @@ struct Ws {
 };
 
 size_t ws_bytes(const WShape &w, int64_t batch_rows, int64_t loss_rows, Ws *out, void *base) {
-    const int64_t G = batch_rows > 0 ? step_wg_bound(w, batch_rows) : 0;
+    const int64_t G = batch_rows > 0 ? pf_rowtile::step_wg_bound(step_tile_cap(w), batch_rows) : 0;
     const int T = eloss_tile(w);
     const int64_t E = (loss_rows > 0 && T > 0) ? (loss_rows + T - 1) / T : 0;
     const size_t a = rnvp::align_up((size_t)G * (w.PG + w.PD) * sizeof(float), 256);
@@ -416,12 +375,6 @@ __global__ __launch_bounds__(FWD_T) void k_critic(WShape w, int T, const float *
     out[row] = o[t];
 }
 
-template <typename K>
-int big_lds(K kernel, size_t bytes, std::atomic<uint64_t> &done) {
-    if (bytes <= 64 * 1024) return PFW_OK;
-    return rnvp::allow_big_lds(reinterpret_cast<const void *>(kernel), (int)kLds, done);
-}
-
 std::atomic<uint64_t> g_lds_step{0}, g_lds_eloss{0}, g_lds_gen{0}, g_lds_crit{0};
 
 int enqueue_step(hipStream_t st, const WShape &w, int kind, float *params, float *sq, const float *x, const float *c,
@@ -506,7 +459,7 @@ int pfw_tiling(const pfw_shape *s, int64_t rows, pfw_tiling_info *out) {
     if (out->step_cap < 1) return PFW_EUNSUPPORTED;
     const Plan st = step_plan(w, rows);
     out->step_tile = st.tile; out->step_wgs = st.wgs; out->step_lds_bytes = (int64_t)st.lds;
-    out->step_wg_bound = step_wg_bound(w, rows);
+    out->step_wg_bound = pf_rowtile::step_wg_bound(out->step_cap, rows);
     return PFW_OK;
 }
 

@@ -8,7 +8,6 @@ which tests/test_cnormal_host.py pins to the fixtures); the GPU's error against 
 holds both numbers per case and quantity (the PARITY lines this file prints).  RNG consumption, lengths and the bitwise
 checks are exact."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -21,6 +20,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import cnormal_torch as ct  # noqa: E402
 import hygiene  # noqa: E402
+import native_libs  # noqa: E402
 from parity import parity  # noqa: E402
 from test_cnormal_host import NAMES, cond_of, fixture_batches, load, restatement  # noqa: E402
 from probaforms_amd.models import _cnormal_lib as N  # noqa: E402
@@ -28,8 +28,7 @@ from probaforms_amd.models.cnormal import ConditionalNormal, Net  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-if not os.path.exists(N.LIB_PATH):    # tests/conftest.py builds only librnvp_hip.so
-    subprocess.check_call(["make", "-C", os.path.dirname(N.LIB_PATH), "-s"])
+native_libs.ensure_built(N)
 
 DEV = torch.device("cuda")
 

@@ -19,11 +19,11 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import cnormal_torch as ct  # noqa: E402
+import native_libs  # noqa: E402
 from probaforms_amd.models import ConditionalNormal, Net  # noqa: E402
 from probaforms_amd.models import _cnormal_lib as N  # noqa: E402
 
-if not os.path.exists(N.LIB_PATH):    # tests/conftest.py builds only librnvp_hip.so
-    subprocess.check_call(["make", "-C", os.path.dirname(N.LIB_PATH), "-s"])
+native_libs.ensure_built(N)
 
 NAMES = ["d1", "default", "indep", "nocond", "sigmoid_deep"]
 

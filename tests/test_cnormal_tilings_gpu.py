@@ -9,7 +9,6 @@ tests/parity.py (for the long chains of tilings_cases.LONG_FAN_IN, e_ref is the 
 kernel-order float32 restatement's).  profiles/r11_tilings_parity.txt holds the REGIME and PARITY lines of one run.  Bitwise claims have no
 tolerance."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -22,14 +21,14 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import cnormal_torch as ct  # noqa: E402
 import hygiene  # noqa: E402
+import native_libs  # noqa: E402
 import tilings_cases as tc  # noqa: E402
 from parity import parity  # noqa: E402
 from probaforms_amd.models import _cnormal_lib as N  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-if not os.path.exists(N.LIB_PATH):    # tests/conftest.py builds only librnvp_hip.so
-    subprocess.check_call(["make", "-C", os.path.dirname(N.LIB_PATH), "-s"])
+native_libs.ensure_built(N)
 
 DEV = torch.device("cuda")
 F32 = torch.float32

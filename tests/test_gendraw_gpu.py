@@ -14,11 +14,15 @@ import pytest
 import torch
 
 import hygiene
+import native_libs
 import predict_edge_series as E
 from cnormal_torch import Normal
+from probaforms_amd.models import _cnormal_lib, _gendraw_lib, _predict_lib, _wgan_lib
 from wgan_torch import Net
 
 pytestmark = pytest.mark.gpu
+
+native_libs.ensure_built(_cnormal_lib, _gendraw_lib, _predict_lib, _wgan_lib)
 
 N, K, ROW0 = 37, 19, 11
 N_TOTAL = N + 20

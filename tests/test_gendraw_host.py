@@ -8,6 +8,11 @@ import numpy as np
 import pytest
 import torch
 
+import native_libs
+from probaforms_amd.models import _cnormal_lib, _gendraw_lib, _predict_lib, _wgan_lib
+
+native_libs.ensure_built(_cnormal_lib, _gendraw_lib, _predict_lib, _wgan_lib)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "probaforms_amd", "models", "gendraw_csrc", "pf_gendraw.h")
 LDS_BYTES = 160 * 1024

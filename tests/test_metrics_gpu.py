@@ -3,7 +3,6 @@ fixtures (tests/golden/metrics_*.npz), an independent float64 numpy restatement 
 on shapes the fixtures do not cover, the global RNG state, bitwise reproducibility and CUDA-tensor inputs."""
 import glob
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -15,12 +14,12 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 sys.path.insert(0, ROOT)
 
 import metrics_numpy as mn  # noqa: E402
+import native_libs  # noqa: E402
 from probaforms_amd.metrics import _lib, fd, frechet_distance, maximum_mean_discrepancy, mmd  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-if not os.path.exists(_lib.LIB_PATH):    # tests/conftest.py builds only librnvp_hip.so
-    subprocess.check_call(["make", "-C", os.path.dirname(_lib.LIB_PATH), "-s"])
+native_libs.ensure_built(_lib)
 
 FIXTURES = sorted(glob.glob(os.path.join(GOLDEN, "metrics_*.npz")))
 

@@ -34,10 +34,14 @@ import numpy as np
 import pytest
 import torch
 
+import native_libs
 import predict_edge_series as E
+from probaforms_amd.models import _predict_lib
 from test_predict_gpu import K, N, ROW0, _close, _dev, _finalize, _model, _setup, _ws
 
 pytestmark = pytest.mark.gpu
+
+native_libs.ensure_built(_predict_lib)
 
 SENTINEL = 0xFFC0DEAD                                                # a NaN payload no arithmetic here produces
 

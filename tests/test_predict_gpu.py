@@ -11,9 +11,14 @@ import functools
 import numpy as np
 import pytest
 import torch
+
+import native_libs
 from conftest import load_case
+from probaforms_amd.models import _predict_lib
 
 pytestmark = pytest.mark.gpu
+
+native_libs.ensure_built(_predict_lib)
 
 NAMES = ["c2", "c3", "c4", "tm", "tm_nocond", "reg1d", "relu_mh"]
 N, K, ROW0 = 37, 19, 11

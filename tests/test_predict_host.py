@@ -7,6 +7,11 @@ import numpy as np
 import pytest
 import torch
 
+import native_libs
+from probaforms_amd.models import _predict_lib
+
+native_libs.ensure_built(_predict_lib)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "probaforms_amd", "models", "predict_csrc", "pf_predict.h")
 

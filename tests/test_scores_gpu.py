@@ -10,14 +10,18 @@ import numpy as np
 import pytest
 import torch
 
+import native_libs
 import scores_numpy as SN
 import scores_series as S
+from probaforms_amd.models import _cnormal_lib, _gendraw_lib, _predict_lib, _wgan_lib
 from test_gendraw_gpu import _fitted
 from test_predict_edges_gpu import SENTINEL, _bits, _guarded, _guards_intact
 from test_predict_gpu import _dev
 from test_scores_host import PROBS, _table
 
 pytestmark = pytest.mark.gpu
+
+native_libs.ensure_built(_cnormal_lib, _gendraw_lib, _predict_lib, _wgan_lib)
 
 
 def _scores(xt, y, probs=PROBS, fair=False, want=("crps", "pit", "q"), bitwise_upload=False):

@@ -7,8 +7,12 @@ import numpy as np
 import pytest
 import torch
 
+import native_libs
 import scores_numpy as SN
 import scores_series as S
+from probaforms_amd.models import _predict_lib
+
+native_libs.ensure_built(_predict_lib)
 
 KS = (1, 2, 3, 19, 256)
 PROBS = (0.0, 0.05, 0.5, 0.95, 1.0)
@@ -221,8 +225,8 @@ def test_pfp_scores_argument_errors_need_no_launch():
 def test_a_library_without_the_entry_point_is_reported_as_missing(monkeypatch):
     """a libpf_predict.so built before pfp_scores existed reports the same pfp_version(): lib() says rebuild, not AttributeError"""
     from probaforms_amd.models import _predict_lib as pl
-    monkeypatch.setattr(pl, "_lib", None)
+    pl.LIBRARY.forget()
     monkeypatch.setitem(pl._SIGNATURES, "pfp_not_there", (C.c_int, []))
     with pytest.raises(pl.PredictLibraryMissing, match="rebuild"):
         pl.lib()
-    assert pl._lib is None
+    assert pl.LIBRARY.loaded is False

@@ -4,7 +4,6 @@ against the grid; the last shape that fits LDS and the first that does not; and 
 tests/tilings_cases.py can see a single dropped row."""
 import ctypes
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -16,15 +15,14 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import cnormal_torch as ct  # noqa: E402
+import native_libs  # noqa: E402
 import tilings_cases as tc  # noqa: E402
 import wgan_torch as wt  # noqa: E402
 from parity import bound  # noqa: E402
 from probaforms_amd.models import _cnormal_lib as N  # noqa: E402
 from probaforms_amd.models import _wgan_lib as W  # noqa: E402
 
-for lib in (W, N):                       # tests/conftest.py builds only librnvp_hip.so
-    if not os.path.exists(lib.LIB_PATH):
-        subprocess.check_call(["make", "-C", os.path.dirname(lib.LIB_PATH), "-s"])
+native_libs.ensure_built(W, N)
 
 LDS = 160 * 1024
 MAX_ROWS = 40000

@@ -4,7 +4,6 @@ shapes the fixtures do not cover; RMSprop and the clamp to the ulp, pfw_fit_epoc
 the seeded public fit + sample, determinism, tensor inputs and API errors."""
 import glob
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -16,14 +15,14 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
+import native_libs  # noqa: E402
 import wgan_torch as wt  # noqa: E402
 from probaforms_amd.models import _wgan_lib as W  # noqa: E402
 from probaforms_amd.models.wgan import ConditionalWGAN, step_kinds  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-if not os.path.exists(W.LIB_PATH):    # tests/conftest.py builds only librnvp_hip.so
-    subprocess.check_call(["make", "-C", os.path.dirname(W.LIB_PATH), "-s"])
+native_libs.ensure_built(W)
 
 FIXTURES = sorted(glob.glob(os.path.join(GOLDEN, "wgan_*.npz")))
 DEV = torch.device("cuda")

@@ -16,6 +16,11 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 HEADER = os.path.join(ROOT, "probaforms_amd", "models", "wgan_csrc", "pf_wgan.h")
 sys.path.insert(0, ROOT)
 
+import native_libs  # noqa: E402
+from probaforms_amd.models import _wgan_lib  # noqa: E402
+
+native_libs.ensure_built(_wgan_lib)
+
 
 def test_fixtures_exist_and_are_small():
     names = sorted(os.path.basename(p) for p in glob.glob(os.path.join(GOLDEN, "wgan_*.npz")))

@@ -11,7 +11,6 @@ magnitude is max |float64 value|; that of a gradient is max(|g|, grad_scale) as 
 two means cancel), and one loss (tilings_cases.TERMS_MAGNITUDE, with its figures) takes the terms of D's last Linear.
 profiles/r11_tilings_parity.txt holds the REGIME and PARITY lines of one run.  Bitwise claims have no tolerance."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -23,6 +22,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import hygiene  # noqa: E402
+import native_libs  # noqa: E402
 import tilings_cases as tc  # noqa: E402
 import wgan_torch as wt  # noqa: E402
 from parity import parity  # noqa: E402
@@ -30,8 +30,7 @@ from probaforms_amd.models import _wgan_lib as W  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-if not os.path.exists(W.LIB_PATH):    # tests/conftest.py builds only librnvp_hip.so
-    subprocess.check_call(["make", "-C", os.path.dirname(W.LIB_PATH), "-s"])
+native_libs.ensure_built(W)
 
 DEV = torch.device("cuda")
 F32, F64 = torch.float32, torch.float64

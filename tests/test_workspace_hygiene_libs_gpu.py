@@ -4,7 +4,6 @@ bindings (one level below the wrappers that allocate their own workspace); all o
 the `zeros` run must meet the reference of the entry point's existing test at that test's bar (named at each check).
 """
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -17,15 +16,14 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import hygiene  # noqa: E402
 import metrics1d_numpy as m1  # noqa: E402
 import metrics_numpy as mn  # noqa: E402
+import native_libs  # noqa: E402
 import wgan_torch as wt  # noqa: E402
 from probaforms_amd.metrics import _boot, _lib, _m1d  # noqa: E402
 from probaforms_amd.models import _wgan_lib as W  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-for _p in (_lib.LIB_PATH, W.LIB_PATH):          # tests/conftest.py builds only librnvp_hip.so
-    if not os.path.exists(_p):
-        subprocess.check_call(["make", "-C", os.path.dirname(_p), "-s"])
+native_libs.ensure_built(_lib, W)
 
 
 def _dev(a, dtype=torch.float32):
