@@ -14,8 +14,9 @@ those of models/_predict.py.
 import torch
 
 from . import _predict
-from ._predict import (SampleScores, SampleStats, ScoreSink, _chunk_quantiles, draw_windows, loop_draws, quantile_row_chunks,
-                       scores_of_draws, stats_of_draws, targets_on_host, validate, validate_scores)
+from ._predict import (JointScores, JointSink, SampleScores, SampleStats, ScoreSink, _chunk_quantiles, draw_windows,
+                       joint_scores_of_draws, loop_draws, quantile_row_chunks, scores_of_draws, stats_of_draws, targets_on_host,
+                       validate, validate_joint, validate_scores)
 
 
 def one_stream(n, width):
@@ -85,12 +86,13 @@ class AffineJob:
                                        k_lo, k_cnt, K, state, x_out, xt)
 
 
-def run(job, Cd, n, K, probs, ddof, want_stats, want_draws, scores=None):
+def run(job, Cd, n, K, probs, ddof, want_stats, want_draws, scores=None, joint=None):
     """-> (SampleStats of device tensors or None, draws [K, n, d] device tensor or None).  The caller has asked
     job.supported().  Quantiles may force row chunks; every chunk then walks the same K noise draws (the generator is
     rewound), so the draws are not kept in that case (want_draws and quantiles are separate public calls).
     scores = (Y, fair): the scores path -- neither statistics nor draws; only the transposed draws are kept, per row chunk,
-    and the first item returned is a SampleScores of device tensors."""
+    and the first item returned is a SampleScores of device tensors.  joint = (Y, fair, order): the same path with a
+    JointSink, and a JointScores of device tensors."""
     from . import _predict_lib as pl
     dev, d, width = job.device, job.d, job.width
     f32 = dict(dtype=torch.float32, device=dev)
@@ -103,6 +105,9 @@ def run(job, Cd, n, K, probs, ddof, want_stats, want_draws, scores=None):
     if scores is not None:
         assert not (want_stats or want_draws)
         sink = ScoreSink(scores[0], n, d, K, probs, scores[1], dev)
+    if joint is not None:
+        assert not (want_stats or want_draws) and scores is None
+        sink = JointSink(joint[0], n, d, K, joint[1], joint[2], dev)
     want_xt = want_q or sink is not None
     chunks = quantile_row_chunks(n, d, K, _predict.XT_CHUNK_BYTES) if want_xt else ([(0, n)] if n else [])
     assert not (want_draws and len(chunks) > 1)
@@ -211,3 +216,14 @@ def sample_scores(model, C, Y, n_draws, quantiles, fair):
     n, Cd = conditions(C)
     s = run(job, Cd, n, K, probs, 0, False, False, scores=(Y, fair))[0]
     return SampleScores(*(None if a is None else a.cpu().numpy() for a in s))
+
+
+def sample_joint_scores(model, C, Y, n_draws, fair, variogram_order):
+    """JointScores of float32 numpy arrays [n]: n_draws samples per condition row scored as vectors against the targets Y"""
+    K, order = validate_joint(n_draws, variogram_order)
+    job, conditions = job_of(model)
+    if not job.supported():
+        return joint_scores_of_draws(loop_draws(model.sample, C, K), targets_on_host(Y), fair, order)
+    n, Cd = conditions(C)
+    s = run(job, Cd, n, K, None, 0, False, False, joint=(Y, fair, order))[0]
+    return JointScores(*(None if a is None else a.cpu().numpy() for a in s))

@@ -10,6 +10,9 @@ the inverse flow and reduces across the draws on the device; only [n, d] statist
 ``sample_scores`` scores those draws against observed targets (CRPS, PIT, quantiles, pinball loss; pfp_scores): the same draws,
 the same sort, one more pass over each sorted series.
 
+``sample_joint_scores`` scores each row's draws as vectors in R^d (energy score, variogram score; pfp_joint_scores): the same
+draws again, one workgroup per row over its K (K - 1) / 2 pairs.
+
 The arithmetic that needs no GPU lives here as plain functions (argument validation, the draw windows, the row chunks, the
 routing between the kernels and the host loop) so that the CPU suite covers it.
 """
@@ -24,6 +27,9 @@ MAX_QUANTILE_DRAWS = 8192         # pf_predict.h PFP_MAX_QUANTILE_DRAWS
 
 SampleStats = collections.namedtuple("SampleStats", "mean std min max quantiles")
 SampleScores = collections.namedtuple("SampleScores", "crps pit quantiles pinball")
+JointScores = collections.namedtuple("JointScores", "energy spread variogram")
+VARIOGRAM_ORDERS = (0.5, 1.0, 2.0)
+PAIR_BLOCK_ELEMS = 1 << 22        # joint_scores_of_draws: elements of the squared-distance block held at once
 
 
 def validate(n_draws, quantiles=None, ddof=0):
@@ -59,6 +65,24 @@ def validate_scores(n_draws, quantiles=None):
         raise ValueError("sample_scores needs n_draws <= %d (one series is sorted inside one workgroup), got %d"
                          % (MAX_QUANTILE_DRAWS, K))
     return K, probs
+
+
+def validate_joint(n_draws, variogram_order=0.5):
+    """-> (K, order) with order None or one of VARIOGRAM_ORDERS as a float; n_draws as validate_scores(); ValueError for any
+    other order (|.|^p is evaluated as sqrt, identity or square, never pow)"""
+    K, _ = validate(n_draws)
+    if K > MAX_QUANTILE_DRAWS:
+        raise ValueError("sample_joint_scores needs n_draws <= %d (one row's pairs are walked by one workgroup), got %d"
+                         % (MAX_QUANTILE_DRAWS, K))
+    if variogram_order is None:
+        return K, None
+    try:
+        order = float(variogram_order)
+    except (TypeError, ValueError):
+        raise ValueError("variogram_order must be None or one of %s, got %r" % (VARIOGRAM_ORDERS, variogram_order))
+    if isinstance(variogram_order, bool) or order not in VARIOGRAM_ORDERS:
+        raise ValueError("variogram_order must be None or one of %s, got %r" % (VARIOGRAM_ORDERS, variogram_order))
+    return K, order
 
 
 def draw_windows(K, n, d, budget=Z_WINDOW_BYTES):
@@ -145,6 +169,59 @@ def scores_of_draws(X, Y, probs, fair):
         return SampleScores(f(crps), f(pit), q, pin)
 
 
+def joint_scores_of_draws(X, Y, fair, order):
+    """JointScores (float32 numpy [n]; variogram None when order is None) of stacked draws X [K, n, d] against the targets
+    Y [n, d]: the host route of ``sample_joint_scores``.  Per row, with draws x_k in R^d and target y, in float64 with one
+    rounding (D = K - 1 if fair else K):
+        spread    = 1/(2 K D) sum_k sum_l |x_k - x_l|_2
+        energy    = 1/K sum_k |x_k - y|_2 - spread
+        variogram = sum_i sum_j (|y_i - y_j|^p - 1/K sum_k |x_ki - x_kj|^p)^2,  p = order
+    The pair sum is blocked over rows and draws: the squared distances of one block are summed column by column, so no
+    K x K x d array is ever held.  A NaN among the row's draws or in its y: all three NaN.  An infinity among the draws: energy
+    and spread NaN (the pair sum's diagonal forms inf - inf); an infinity among the draws or in y: variogram NaN (its (i, i)
+    terms do)."""
+    X64 = np.asarray(X, dtype=np.float32).astype(np.float64)
+    Y32 = np.asarray(Y, dtype=np.float32)
+    if X64.ndim != 3 or Y32.shape != X64.shape[1:]:
+        raise ValueError("Y must have shape %s (one target per condition row and column), got %s"
+                         % (X64.shape[1:], Y32.shape))
+    Y64 = Y32.astype(np.float64)
+    K, n, d = X64.shape
+    f = lambda a: np.asarray(a, dtype=np.float32)
+    pw = {0.5: np.sqrt, 1.0: lambda a: a, 2.0: np.square, None: None}[order]
+    with np.errstate(all="ignore"):
+        nan = np.isnan(X64).any(axis=(0, 2)) | np.isnan(Y64).any(axis=1)
+        xinf = np.isinf(X64).any(axis=(0, 2))
+        t1 = np.sqrt(np.square(X64 - Y64).sum(axis=2)).sum(axis=0)
+        pairs = np.zeros(n)
+        cols = np.ascontiguousarray(X64.transpose(2, 0, 1))          # [d, K, n]
+        kb = max(1, min(K, 256))
+        rows = max(1, PAIR_BLOCK_ELEMS // (kb * K))
+        for r0 in range(0, n, rows):
+            for lo in range(0, K, kb):
+                sq = np.zeros((min(kb, K - lo), K, min(rows, n - r0)))
+                df = np.empty_like(sq)
+                for j in range(d):
+                    col = cols[j, :, r0:r0 + rows]
+                    np.subtract(col[lo:lo + kb, None], col[None], out=df)
+                    np.square(df, out=df)
+                    sq += df
+                pairs[r0:r0 + rows] += np.sqrt(sq, out=sq).sum(axis=(0, 1))
+        spread = pairs / (2.0 * K * float(K - 1 if fair else K))
+        energy = t1 / K - spread
+        dead = nan | xinf
+        energy, spread = np.where(dead, np.nan, energy), np.where(dead, np.nan, spread)
+        vario = None
+        if order is not None:
+            vario = np.zeros(n)
+            for i in range(d):
+                for j in range(i + 1, d):
+                    m = pw(np.abs(X64[:, :, i] - X64[:, :, j])).sum(axis=0) / K
+                    vario += 2.0 * np.square(pw(np.abs(Y64[:, i] - Y64[:, j])) - m)
+            vario = f(np.where(nan | xinf | np.isinf(Y64).any(axis=1), np.nan, vario))
+        return JointScores(f(energy), f(spread), vario)
+
+
 def targets_on_host(Y):
     """the observed targets as float32 numpy, for the host route"""
     if isinstance(Y, torch.Tensor):
@@ -191,6 +268,29 @@ class ScoreSink:
         return SampleScores(self.crps, self.pit, self.q, self.pinball)
 
 
+class JointSink:
+    """the joint-scores path of both run() functions, with ScoreSink's protocol: the device outputs, and pfp_joint_scores on
+    one row chunk's transposed draws"""
+
+    def __init__(self, Y, n, d, K, fair, order, device):
+        self.Y = targets_on_device(Y, device)
+        if tuple(self.Y.shape) != (n, d):
+            raise ValueError("Y must have shape (%d, %d) (one target per condition row and column), got %s"
+                             % (n, d, tuple(self.Y.shape)))
+        f32 = dict(dtype=torch.float32, device=device)
+        self.n, self.d, self.K, self.fair, self.order = n, d, K, bool(fair), order
+        self.energy, self.spread = torch.empty((n,), **f32), torch.empty((n,), **f32)
+        self.variogram = None if order is None else torch.empty((n,), **f32)
+
+    def chunk(self, pl, xt, lo, m):
+        """joint scores of rows lo .. lo + m"""
+        pl.joint_scores(xt, self.Y[lo:lo + m], m, self.d, self.K, self.fair, self.order, self.energy[lo:lo + m],
+                        self.spread[lo:lo + m], None if self.variogram is None else self.variogram[lo:lo + m])
+
+    def result(self):
+        return JointScores(self.energy, self.spread, self.variogram)
+
+
 def _conditions(nf, C, eng):
     if type(C) == type(1):            # python int only, as nflow.py:135
         return C, None
@@ -203,10 +303,11 @@ def _host_draws(n, d, dev):
     return "device" if (n * d >= 16 and HostStreamOnDevice.usable(dev)) else "host"
 
 
-def run(nf, C, K, probs, ddof, want_stats, want_draws, scores=None):
+def run(nf, C, K, probs, ddof, want_stats, want_draws, scores=None, joint=None):
     """-> (SampleStats of device tensors or None, draws [K, n, d] device tensor or None).  The caller has checked route().
     scores = (Y, fair): the scores path -- neither statistics nor draws; only the transposed draws are kept, per row chunk,
-    and the first item returned is a SampleScores of device tensors."""
+    and the first item returned is a SampleScores of device tensors.  joint = (Y, fair, order): the same path with a
+    JointSink, and a JointScores of device tensors."""
     from . import _predict_lib as pl
     from .nflow import HostStreamOnDevice
     eng = nf.engine()
@@ -224,6 +325,9 @@ def run(nf, C, K, probs, ddof, want_stats, want_draws, scores=None):
     if scores is not None:
         assert not (want_stats or want_draws)
         sink = ScoreSink(scores[0], n, d, K, probs, scores[1], dev)
+    if joint is not None:
+        assert not (want_stats or want_draws) and scores is None
+        sink = JointSink(joint[0], n, d, K, joint[1], joint[2], dev)
     want_xt = q_out is not None or sink is not None
     chunks = quantile_row_chunks(n, d, K, XT_CHUNK_BYTES) if want_xt else ([(0, n)] if n else [])
     keep = []

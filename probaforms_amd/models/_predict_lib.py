@@ -24,6 +24,13 @@ LIB_PATH = os.path.join(_HERE, "predict_csrc", "libpf_predict.so")
 
 _VP, _I64, _I32, _SZ, _SP = C.c_void_p, C.c_int64, C.c_int32, C.c_size_t, C.POINTER(RnvpShape)
 
+
+class JointTile(C.Structure):
+    """pfp_joint_tile: how pfp_joint_scores walks one row of (d, K)"""
+    _fields_ = [(name, _I32) for name in ("tile_draws", "n_tiles", "chunk_cols", "n_chunks", "budget_bytes", "lds_bytes",
+                                          "threads", "max_grid")]
+
+
 _SIGNATURES = {
     "pfp_version": (C.c_int, []),
     "pfp_status_string": (C.c_char_p, [C.c_int]),
@@ -33,6 +40,8 @@ _SIGNATURES = {
     "pfp_finalize": (C.c_int, [_VP, _VP, _I64, _I32, _I32, _VP, _VP, _VP, _VP]),
     "pfp_quantiles": (C.c_int, [_VP, _VP, _I64, _I32, _I64, _VP, _I32, _VP]),
     "pfp_scores": (C.c_int, [_VP, _VP, _VP, _I64, _I32, _I64, _I32, _VP, _I32, _VP, _VP, _VP, _VP]),
+    "pfp_joint_scores": (C.c_int, [_VP, _VP, _VP, _I64, _I32, _I64, _I32, C.c_double, _VP, _VP, _VP]),
+    "pfp_joint_tiling": (C.c_int, [_I32, _I64, C.POINTER(JointTile)]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -104,3 +113,20 @@ def scores(xt, y, n_rows, d, k_total, fair, probs, crps, pit, q_out, pinball):
     check(lib().pfp_scores(_stream(), px, py, int(n_rows), int(d), int(k_total), int(bool(fair)),
                            _ptr(probs, torch.float64, "probs", True) if nq else None, nq, _f32(crps, "crps", True),
                            _f32(pit, "pit", True), _f32(q_out, "q_out", True), _f32(pinball, "pinball", True)), "pfp_scores")
+
+
+def joint_scores(xt, y, n_rows, d, k_total, fair, variogram_order, energy, spread, variogram):
+    """xt [n_rows, d, k_total], y [n_rows, d] float32; energy, spread, variogram [n_rows] float32, each nullable;
+    variogram_order 0.5, 1 or 2 (anything when variogram is None)"""
+    py, px = _f32(y, "y"), _f32(xt, "xt")
+    order = 0.5 if variogram_order is None else float(variogram_order)
+    check(lib().pfp_joint_scores(_stream(), px, py, int(n_rows), int(d), int(k_total), int(bool(fair)), order,
+                                 _f32(energy, "energy", True), _f32(spread, "spread", True),
+                                 _f32(variogram, "variogram", True)), "pfp_joint_scores")
+
+
+def joint_tiling(d, k_total):
+    """JointTile of one row of (d, k_total): decided on the host, no GPU"""
+    t = JointTile()
+    check(lib().pfp_joint_tiling(int(d), int(k_total), C.byref(t)), "pfp_joint_tiling")
+    return t

@@ -225,3 +225,14 @@ class ConditionalNormal(GenModel):
         shape is not (n, d) raise ValueError."""
         from . import _gendraw
         return _gendraw.sample_scores(self, C, Y, n_draws, quantiles, fair)
+
+    def sample_joint_scores(self, C, Y, n_draws=1000, fair=False, variogram_order=0.5):
+        """Joint scores of the predictive draws against the observed targets ``Y`` [n, d], as ``RealNVP.sample_joint_scores``:
+        ``JointScores(energy, spread, variogram)`` of float32 numpy arrays [n] (variogram None when ``variogram_order`` is
+        None), each row's draws scored as vectors in R^d.  The noise draws come from torch's global CPU generator exactly as
+        ``n_draws`` successive ``sample(C)`` calls draw them, so a seeded call scores the draws a seeded ``sample_many``
+        returns; the generator and the scores run on the device.  ``n_draws < 1``, ``n_draws > 8192``, an order other than
+        0.5, 1 or 2, or a ``Y`` whose shape is not (n, d) raise ValueError.
+        A width the kernel does not serve falls back to the loop on the host (``self.sample`` n_draws times plus numpy)."""
+        from . import _gendraw
+        return _gendraw.sample_joint_scores(self, C, Y, n_draws, fair, variogram_order)

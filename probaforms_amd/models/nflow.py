@@ -389,6 +389,25 @@ class NormalizingFlow(nn.Module):
                 return _predict.SampleScores(*(None if a is None else torch.from_numpy(a).to(DEVICE) for a in s))
             return _predict.run(self, C, K, probs, 0, False, False, scores=(Y, fair))[0]
 
+    def sample_joint_scores(self, C, Y, n_draws=1000, fair=False, variogram_order=0.5):
+        """Per condition row, the joint scores of ``n_draws`` samples, taken as vectors in R^var_size, against the observed
+        targets ``Y`` [n, var_size]: ``JointScores(energy, spread, variogram)`` of float32 device tensors [n] (variogram None
+        when ``variogram_order`` is None).  energy = mean |x - y|_2 - spread, spread = mean |x - x'|_2 / 2 over the draws
+        (``fair=True``: the pair mean over the K (K - 1) distinct pairs); variogram = sum_ij (|y_i - y_j|^p - mean |x_i -
+        x_j|^p)^2 with p = ``variogram_order`` in (0.5, 1, 2).  The draws are those of ``sample_many``, scored on the device
+        in float64 with one rounding (pfp_joint_scores).  Consumes torch's global CPU generator exactly as the loop of
+        ``sample(C)`` calls does.  ``n_draws < 1``, ``n_draws > 8192``, any other order or a ``Y`` whose shape is not
+        (n, var_size) raise ValueError.  A layer-wise flow, a user-assigned prior and a shape the kernel does not hold in LDS
+        fall back to that loop on the host (``sample`` n_draws times plus numpy)."""
+        from . import _predict
+        K, order = _predict.validate_joint(n_draws, variogram_order)
+        with torch.no_grad():
+            if self._predict_route() != "kernel":
+                X = _predict.loop_draws(lambda c: torch.as_tensor(self.sample(c)).detach().cpu().numpy(), C, K)
+                s = _predict.joint_scores_of_draws(X, _predict.targets_on_host(Y), fair, order)
+                return _predict.JointScores(*(None if a is None else torch.from_numpy(a).to(DEVICE) for a in s))
+            return _predict.run(self, C, K, None, 0, False, False, joint=(Y, fair, order))[0]
+
     # -- host staging (SURVEY.md 8(f) rank 3) -------------------------------------------------
     # one chunk of output rows: at least PIPELINE_CHUNK_BYTES and at least PIPELINE_MIN_ROWS rows (a launch of fewer
     # rows leaves CUs idle: 256 rows per workgroup).  Measured at API level, C2 sample(1M): 8 MB chunks 3.1 ms (device

@@ -9,6 +9,8 @@
  *   pfp_finalize          running moments -> mean, std, min, max
  *   pfp_quantiles         exact quantiles (numpy's default 'linear') of the transposed draws
  *   pfp_scores            CRPS, PIT, quantiles and pinball losses of the transposed draws against observed targets
+ *   pfp_joint_scores      energy score and variogram score of each row's draws as vectors in R^d (pf_joint.hip)
+ *   pfp_joint_tiling      how pfp_joint_scores walks a row of (d, K): host only
  *
  * Conventions (as pf_cnormal.h)
  *   - every array is a DEVICE pointer unless it says HOST; sizes are plain integers;
@@ -46,7 +48,8 @@ extern "C" {
 
 #define PFP_VERSION 101         /* pfp_version(): bumped whenever an argument list or the state's layout or meaning changes */
 
-#define PFP_MAX_QUANTILE_DRAWS 8192   /* pfp_quantiles / pfp_scores sort one (row, column) series inside one workgroup's LDS */
+#define PFP_MAX_QUANTILE_DRAWS 8192   /* pfp_quantiles / pfp_scores sort one (row, column) series inside one workgroup's LDS;
+                                         pfp_joint_scores bounds one workgroup's O(K^2) pair loop by the same number */
 
 /*
  * Running moments of one (row, column): PFP_STATE_BYTES bytes, all zero = nothing seen yet.
@@ -126,6 +129,48 @@ int pfp_quantiles(void *stream, const float *xt, int64_t n_rows, int32_t d, int6
 int pfp_scores(void *stream, const float *xt, const float *y, int64_t n_rows, int32_t d, int64_t k_total,
                int32_t fair, const double *probs, int32_t n_probs,
                float *crps, float *pit, float *q_out, float *pinball);
+
+/*
+ * Joint scores of every row's draws x_1 .. x_K = xt[r][:][k] in R^d against its target y[r][:], in float64 from the float32
+ * values (every difference, square, sum and square root; the sums of squares over the d columns included) with one rounding
+ * to float32 (D = K, or K - 1 when fair != 0):
+ *   spread[r]    = 1/(2 K D) sum_k sum_l |x_k - x_l|_2                                   (fair and K = 1: NaN, 0 / 0)
+ *   energy[r]    = 1/K sum_k |x_k - y|_2  -  spread[r]            (Gneiting & Raftery 2007; at d = 1 the crps of pfp_scores)
+ *   variogram[r] = sum_i sum_j ( |y_i - y_j|^p - 1/K sum_k |x_ki - x_kj|^p )^2           (Scheuerer & Hamill 2015, unit
+ *                  weights, p = variogram_order; 0 when d = 1)
+ * xt [n_rows, d, k_total] (pfp_draw_accumulate's xt_out) and y [n_rows, d] are not modified; energy, spread and variogram
+ * [n_rows] are each nullable, and what is not asked for is not computed (no variogram: no O(K d^2) pass; neither energy nor
+ * spread: no pair loop).  variogram_order is 0.5, 1 or 2, evaluated as sqrt, identity or square; it is ignored when variogram
+ * is NULL and PFP_EINVAL otherwise.  1 <= k_total <= PFP_MAX_QUANTILE_DRAWS (PFP_EUNSUPPORTED above); every d >= 1 is served.
+ * One workgroup per row, the draws staged through LDS as pfp_joint_tiling reports; each unordered pair of draws is visited
+ * once; per-thread float64 partials are combined by a fixed halving tree, no atomics: the order of every sum depends on
+ * (d, k_total) alone, so a row's results are bitwise the same in any call, any grid and any split of the rows over calls.
+ * Non-finite values: a NaN among the row's draws or in its y makes all three outputs NaN.  A row whose draws hold an infinity
+ * has energy and spread NaN (the pair sum's diagonal forms inf - inf; it is not summed, so this is set explicitly); a finite
+ * row with an infinity in y has energy +inf.  The variogram's (i, i) terms form inf - inf as soon as the row's draws or its y
+ * hold an infinity: it is then NaN (set explicitly, the diagonal is not summed either).  Nothing leaves its row.
+ */
+int pfp_joint_scores(void *stream, const float *xt, const float *y, int64_t n_rows, int32_t d, int64_t k_total,
+                     int32_t fair, double variogram_order, float *energy, float *spread, float *variogram);
+
+/*
+ * How pfp_joint_scores walks one row of (d, k_total).  The draws' images [column][draw] and y share budget_bytes of LDS:
+ *   n_tiles == 1                  d (K + 1) floats fit: the whole row is one image, tile_draws == k_total
+ *   n_tiles  > 1, n_chunks == 1   tiles of tile_draws draws (a multiple of 64), two images of all d columns
+ *   n_chunks > 1                  even two 64-draw images of all columns do not fit: tile_draws == 64 and the columns pass
+ *                                 through in n_chunks chunks of chunk_cols
+ * lds_bytes is one workgroup's dynamic LDS (the reduction scratch included), threads its size, max_grid the largest grid: more
+ * rows than that are served by the grid stride.
+ */
+typedef struct {
+    int32_t tile_draws, n_tiles;
+    int32_t chunk_cols, n_chunks;
+    int32_t budget_bytes, lds_bytes;
+    int32_t threads, max_grid;
+} pfp_joint_tile;
+
+/* host only, no GPU.  PFP_EINVAL for NULL out, d < 1 or k_total < 1; PFP_EUNSUPPORTED for k_total > PFP_MAX_QUANTILE_DRAWS */
+int pfp_joint_tiling(int32_t d, int64_t k_total, pfp_joint_tile *out);
 
 #ifdef __cplusplus
 }

@@ -23,6 +23,8 @@
 //
 // k_quantiles / k_scores: one 256-thread workgroup per (row, column) series of the transposed draws sorts it in LDS; quantiles,
 // and the CRPS / PIT / pinball scores against an observed target, are one pass over the sorted series (see the kernels).
+//
+// k_joint (pfp_joint_scores, pfp_joint_tiling): pf_joint.hip, the second object of this library.
 #include "../../csrc/rnvp_common.h"
 #include "../../csrc/rnvp_generic_net.h"
 #include "../../csrc/rnvp_prior.h"

@@ -335,6 +335,31 @@ class RealNVP(GenModel):
         s = self.nf.sample_scores(C, Y, K, probs, fair)
         return _predict.SampleScores(*(None if a is None else a.cpu().numpy() for a in s))
 
+    def sample_joint_scores(self, C, Y, n_draws=1000, fair=False, variogram_order=0.5):
+        """Scores of the JOINT predictive distribution of every condition row against what was observed (a name the reference
+        does not have).  ``sample_scores`` scores every column on its own and cannot see the dependence between columns;
+        here each row's ``n_draws`` samples x_k are vectors in R^d.  Returns ``JointScores(energy, spread, variogram)``: float32
+        numpy arrays [n].  energy = mean |x_k - y|_2 - spread is the energy score (the multivariate CRPS; at d = 1 the crps of
+        ``sample_scores``), spread = mean |x_k - x_l|_2 / 2 over the pairs of draws (``fair=True``: over the K (K - 1)
+        distinct pairs; NaN for one draw).  variogram = sum_ij (|y_i - y_j|^p - mean_k |x_ki - x_kj|^p)^2 with
+        p = ``variogram_order`` (0.5, 1 or 2) is the variogram score, the one sensitive to a wrong correlation structure;
+        ``variogram_order=None`` skips it and returns None in its place.  float64 arithmetic from the float32 draws, one
+        rounding.  A NaN among a row's draws or in its y makes that row's scores NaN and touches no other.  ``C`` is an array
+        or a python int, as in ``sample``; ``Y`` [n, d] is numpy, array-like or a torch tensor (a tensor on the device stays
+        there).  Consumes torch's global CPU generator exactly as the loop of ``sample(C)`` calls does, so a seeded call
+        scores the draws a seeded ``sample_many`` returns and leaves the generator where the loop leaves it.
+        ``n_draws < 1``, ``n_draws > 8192``, any other order or a ``Y`` whose shape is not (n, d) raise ValueError.  A
+        layer-wise flow, a user-assigned prior and a shape the kernel does not hold in LDS fall back to the loop on the host
+        (``self.sample`` n_draws times plus numpy), so the call always works."""
+        from . import _predict
+        K, order = _predict.validate_joint(n_draws, variogram_order)
+        if self.nf._predict_route() != "kernel":
+            return _predict.joint_scores_of_draws(_predict.loop_draws(self.sample, C, K), _predict.targets_on_host(Y), fair, order)
+        if type(C) != type(1):
+            C = _to_device_f32(C, self.nf.engine().device)
+        s = self.nf.sample_joint_scores(C, Y, K, fair, order)
+        return _predict.JointScores(*(None if a is None else a.cpu().numpy() for a in s))
+
     def _sample_sharded(self, C, n, rank, world, gather):
         import torch.distributed as dist
         eng = self.nf.engine()
