@@ -33,6 +33,9 @@ _SIGNATURES = {
     "pfm_metric1d_workspace_bytes": (_SZ, [C.c_int, _I64, _I64, _I64, _I64, _I64]),
     "pfm_metric1d": (C.c_int, [_VP, C.c_int, _VP, _VP, _VP, _VP, _I64, _I64, _I64, _VP, _VP, _I64, _I64, C.c_double,
                                C.c_double, _VP, _VP, _SZ]),
+    "pfm_project": (C.c_int, [_VP, _VP, _I64, _VP, _I64, _I64, _VP, _I64, _VP]),
+    "pfm_wasserstein1d_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64, C.c_int]),
+    "pfm_wasserstein1d": (C.c_int, [_VP, C.c_int, _VP, _VP, _VP, _VP, _I64, _I64, _I64, _VP, _VP, _I64, _VP, _VP, _SZ]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -100,3 +103,37 @@ def metric1d_status(metric, cols, perm, gstart, ngroups, nr, nf, idx_r, idx_f, r
 
 def metric1d(*args):
     check(metric1d_status(*args), "pfm_metric1d")
+
+
+def project(Xr, Xf, theta, cols):
+    """enqueue cols[k, i] = sum_j [Xr; Xf][i, j] * theta[k, j] (feature order, product and sum rounded separately) on
+    the current stream; cols [n_proj, nr + nf] float64"""
+    nr, d = Xr.shape
+    nf = Xf.shape[0]
+    n_proj = theta.shape[0]
+    assert Xf.shape[1] == d == theta.shape[1] and tuple(cols.shape) == (n_proj, nr + nf)
+    st = lib().pfm_project(torch.cuda.current_stream().cuda_stream, _ptr(Xr, torch.float64, "X_real"), nr,
+                           _ptr(Xf, torch.float64, "X_fake"), nf, d, _ptr(theta, torch.float64, "theta"), n_proj,
+                           _ptr(cols, torch.float64, "cols"))
+    check(st, "pfm_project")
+
+
+def wasserstein1d_workspace_bytes(nr, nf, d, reps, p):
+    return int(lib().pfm_wasserstein1d_workspace_bytes(int(nr), int(nf), int(d), int(reps), int(p)))
+
+
+def wasserstein1d_status(p, cols, perm, gstart, ngroups, nr, nf, idx_r, idx_f, reps, out, ws):
+    """enqueue W_p^p of `reps` replicates of every pooled column on the current stream and return the status; `out` is a
+    float64 view of reps * d elements"""
+    d = cols.shape[0]
+    assert idx_r.numel() == reps * nr and idx_f.numel() == reps * nf and cols.shape[1] == nr + nf
+    assert out.numel() == reps * d
+    return int(lib().pfm_wasserstein1d(torch.cuda.current_stream().cuda_stream, int(p), _ptr(cols, torch.float64, "cols"),
+                                       _ptr(perm, torch.int32, "perm"), _ptr(gstart, torch.int32, "gstart"),
+                                       _ptr(ngroups, torch.int32, "ngroups"), int(nr), int(nf), int(d),
+                                       _ptr(idx_r, torch.int32, "idx_real"), _ptr(idx_f, torch.int32, "idx_fake"), int(reps),
+                                       _ptr(out, torch.float64, "out"), _ptr(ws, torch.uint8, "workspace"), ws.numel()))
+
+
+def wasserstein1d(*args):
+    check(wasserstein1d_status(*args), "pfm_wasserstein1d")

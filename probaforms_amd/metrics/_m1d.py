@@ -41,11 +41,20 @@ class Pooled:
     the tie groups of that order as gstart [d, N + 1] and ngroups [d] (int32)"""
 
     def __init__(self, Xr, Xf):
-        self.nr, self.d = Xr.shape
-        self.nf = Xf.shape[0]
-        N = self.nr + self.nf
-        self.device = Xr.device
-        self.cols = torch.cat([Xr, Xf], dim=0).t().contiguous()
+        self._order(torch.cat([Xr, Xf], dim=0).t().contiguous(), Xr.shape[0])
+
+    @classmethod
+    def from_columns(cls, cols, nr):
+        """of ready-made pooled columns [d, nr + nf] (the first nr entries of each are the real sample's)"""
+        p = cls.__new__(cls)
+        p._order(cols.contiguous(), nr)
+        return p
+
+    def _order(self, cols, nr):
+        self.d, N = cols.shape
+        self.nr, self.nf = nr, N - nr
+        self.device = cols.device
+        self.cols = cols
         vals, perm = torch.sort(self.cols, dim=1, stable=True)
         self.perm = perm.to(torch.int32).contiguous()
         new = torch.ones_like(vals, dtype=torch.bool)

@@ -11,6 +11,9 @@
  *   pfm_metric1d      the per-feature rank and density statistics behind the eight 1-D
  *                     metrics (probaforms/metrics/ks1d.py, div1d.py), from the pooled
  *                     column's sorted order and the replicate's draw counts
+ *   pfm_wasserstein1d the 1-D Wasserstein distance W_p^p (p = 1, 2) of every replicate's columns, from the
+ *                     same sorted order and draw counts; pfm_project makes such columns of a
+ *                     multivariate sample's projections (sliced Wasserstein distance)
  *
  * Conventions (as include/rnvp_hip.h)
  *   - every pointer is a DEVICE pointer; sizes are plain integers;
@@ -39,7 +42,8 @@ extern "C" {
 
 #define PFM_OK            0
 #define PFM_EINVAL       (-1)   /* NULL pointer, non-positive size, index range       */
-#define PFM_EUNSUPPORTED (-2)   /* d too large for the moments kernels' LDS row tile    */
+#define PFM_EUNSUPPORTED (-2)   /* d too large for the moments kernels' LDS row tile;
+                                   a Wasserstein order p other than 1 or 2              */
 #define PFM_EWORKSPACE   (-3)   /* workspace smaller than *_workspace_bytes() says      */
 
 #define PFM_VERSION 101         /* pfm_version(): bumped whenever an argument list changes */
@@ -113,6 +117,29 @@ int pfm_metric1d(void *stream, int metric, const double *cols, const int32_t *pe
                  const int32_t *ngroups, int64_t nr, int64_t nf, int64_t d, const int32_t *idx_r,
                  const int32_t *idx_f, int64_t reps, int64_t bins, double h_r, double h_f, void *out,
                  void *workspace, size_t workspace_bytes);
+
+/* ---- Wasserstein distances (pf_wasserstein.hip) ------------------------------------------- */
+
+/*
+ * The pooled columns of n_proj projections: cols[k, i] = sum_j Z[i, j] theta[k, j] with Z = [Xr; Xf]
+ * (real rows first), cols [n_proj, nr + nf], theta [n_proj, d], all float64 row-major.  The sum
+ * starts at 0 and runs over j in order, the product and the sum rounded separately (no fma).
+ */
+int pfm_project(void *stream, const double *Xr, int64_t nr, const double *Xf, int64_t nf, int64_t d,
+                const double *theta, int64_t n_proj, double *cols);
+
+/* bytes of workspace pfm_wasserstein1d needs (0: the arguments are invalid, p not 1 or 2 included) */
+size_t pfm_wasserstein1d_workspace_bytes(int64_t nr, int64_t nf, int64_t d, int64_t reps, int p);
+
+/*
+ * `reps` replicates, every column: out[r * d + f] = W_p^p = int_0^1 |Q_r(u) - Q_f(u)|^p du between the
+ * empirical distributions of the two resampled columns (for p = 1 scipy.stats.wasserstein_distance);
+ * the caller takes the p-th root.  cols / perm / gstart / ngroups, idx_r / idx_f as pfm_metric1d.
+ * Returns PFM_EUNSUPPORTED for a p other than 1 or 2.
+ */
+int pfm_wasserstein1d(void *stream, int p, const double *cols, const int32_t *perm, const int32_t *gstart,
+                      const int32_t *ngroups, int64_t nr, int64_t nf, int64_t d, const int32_t *idx_r,
+                      const int32_t *idx_f, int64_t reps, double *out, void *workspace, size_t workspace_bytes);
 
 #ifdef __cplusplus
 }

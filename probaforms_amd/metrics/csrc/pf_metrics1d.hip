@@ -23,22 +23,13 @@
 #include <stdint.h>
 
 #include "pf_metrics.h"
-
-#define PFM_TRY(x)                                              \
-    do {                                                        \
-        hipError_t e_ = (x);                                    \
-        if (e_ != hipSuccess) return (int)e_;                   \
-    } while (0)
+#include "pf_scan1d.h"
 
 namespace {
 
-constexpr int NT = 256;          // threads per workgroup, every kernel
-constexpr int IPT = 4;           // tie groups per thread per chunk of the scan
 constexpr int GP = 8;            // grid points per KDE workgroup
 constexpr int HIST_LDS = 2048;   // bins counted in LDS (more go straight to global memory)
 constexpr int64_t CVM_MAX_N = int64_t(1) << 20;   // sum (2R - 2i)^2 <= n (2N)^2 < 2^63: exact in 64 bits
-
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // numpy.linspace(start, stop, num)[k] (endpoint=True): k * step + start with step = (stop - start) / (num - 1), or
 // (k / div) * delta + start where step underflows to 0; the last point is `stop` itself
@@ -56,40 +47,6 @@ __device__ inline double linspace_at(int64_t k, int64_t num, double start, doubl
     if (num > 1 && k == num - 1) y = stop;
     return y;
 }
-
-__global__ void __launch_bounds__(NT) k_counts(const int32_t *idx_r, const int32_t *idx_f, int64_t nr, int64_t nf,
-                                               int32_t *cnt) {
-    const int64_t rep = blockIdx.y, N = nr + nf;
-    int32_t *c = cnt + rep * N;
-    for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < N; i += (int64_t)gridDim.x * NT) {
-        if (i < nr) {
-            const int32_t j = idx_r[rep * nr + i];
-            if ((uint32_t)j < (uint32_t)nr) atomicAdd(&c[j], 1);
-        } else {
-            const int32_t j = idx_f[rep * nf + (i - nr)];
-            if ((uint32_t)j < (uint32_t)nf) atomicAdd(&c[nr + j], 1);
-        }
-    }
-}
-
-struct Feature {                 // one (feature, replicate): the sorted order, its tie groups, the draw counts
-    const double *col;           // pooled original column [N]
-    const int32_t *perm, *gs;    // sorted position -> pooled row [N]; group g = positions gs[g] .. gs[g + 1] - 1
-    const int32_t *cnt;          // draw count of each pooled row [N]
-    int64_t nr, N;
-    int G;
-    __device__ void counts(int g, int64_t &l, int64_t &ar) const {
-        l = 0;
-        ar = 0;
-        for (int32_t k = gs[g]; k < gs[g + 1]; ++k) {
-            const int32_t row = perm[k];
-            const int64_t v = cnt[row];
-            l += v;
-            if (row < nr) ar += v;
-        }
-    }
-    __device__ double value(int g) const { return col[perm[gs[g]]]; }
-};
 
 // value of the first (last = false) or last non-empty group: the replicate's pooled minimum / maximum
 __device__ double extreme(const Feature &z, bool last, int *sh) {
@@ -113,41 +70,6 @@ __device__ double extreme(const Feature &z, bool last, int *sh) {
         if (last ? g >= 0 : g < z.G) return z.value(g);
     }
     return 0.0;                  // unreachable: every replicate draws rows
-}
-
-// inclusive block scan of (a, b) over the workgroup's threads; returns the exclusive prefix, totals in ta / tb
-__device__ void block_scan2(int64_t a, int64_t b, int64_t &ea, int64_t &eb, int64_t &ta, int64_t &tb, int64_t *sa,
-                            int64_t *sb) {
-    const int tid = threadIdx.x;
-    sa[tid] = a;
-    sb[tid] = b;
-    __syncthreads();
-    for (int off = 1; off < NT; off <<= 1) {
-        const int64_t xa = tid >= off ? sa[tid - off] : 0, xb = tid >= off ? sb[tid - off] : 0;
-        __syncthreads();
-        sa[tid] += xa;
-        sb[tid] += xb;
-        __syncthreads();
-    }
-    ea = sa[tid] - a;
-    eb = sb[tid] - b;
-    ta = sa[NT - 1];
-    tb = sb[NT - 1];
-    __syncthreads();
-}
-
-// fixed-order tree sum of one double per thread; every thread gets the total
-__device__ double block_sum(double v, double *sd) {
-    const int tid = threadIdx.x;
-    sd[tid] = v;
-    __syncthreads();
-    for (int off = NT / 2; off > 0; off >>= 1) {
-        if (tid < off) sd[tid] = sd[tid] + sd[tid + off];
-        __syncthreads();
-    }
-    const double s = sd[0];
-    __syncthreads();
-    return s;
 }
 
 template <int M>
