@@ -16,6 +16,13 @@ The eight 1-D metrics of the reference live in the reference's module paths, not
     from probaforms_amd.metrics.div1d import kullback_leibler_1d, jensen_shannon_1d           # histograms, bins=10
     from probaforms_amd.metrics.div1d import kullback_leibler_1d_kde, jensen_shannon_1d_kde   # Gaussian KDE, bins=101
 
+The metrics the reference does not have are modules of their own, outside the export list as well: the Wasserstein distances
+(wasserstein.py) and k-nearest-neighbour precision, recall, density and coverage, which say in which way a generated sample is
+wrong (fidelity against diversity) where the distances only say how much:
+
+    from probaforms_amd.metrics.wasserstein import wasserstein_1d, sliced_wasserstein_distance
+    from probaforms_amd.metrics.prdc import prdc, prdc_full_sample     # bootstrapped (mean, std) pairs; the samples as given
+
 `__all__` and the `probaforms.metrics` alias (`probaforms_amd.install_as_probaforms()`) name only the two
 multivariate metrics, so `from probaforms.metrics import kolmogorov_smirnov_1d` raises ImportError there.
 """

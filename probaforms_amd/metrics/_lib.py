@@ -16,6 +16,7 @@ MOMENTS_MAX_D = 4096       # PFM_MOMENTS_MAX_D
 # pfm_metric1d's statistics (pf_metrics.h PFM_M1D_*)
 M1D_KS, M1D_CVM, M1D_AD, M1D_AUC, M1D_HIST, M1D_KDE = range(6)
 CVM_MAX_N = 1 << 20        # pooled rows pfm_metric1d's Cramer-von Mises sums hold exactly
+KNN_MAX_K = 16             # PFM_KNN_MAX_K: the largest nearest_k of pfm_prdc
 PFM_EUNSUPPORTED, PFM_EWORKSPACE = -2, -3
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -36,6 +37,8 @@ _SIGNATURES = {
     "pfm_project": (C.c_int, [_VP, _VP, _I64, _VP, _I64, _I64, _VP, _I64, _VP]),
     "pfm_wasserstein1d_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64, C.c_int]),
     "pfm_wasserstein1d": (C.c_int, [_VP, C.c_int, _VP, _VP, _VP, _VP, _I64, _I64, _I64, _VP, _VP, _I64, _VP, _VP, _SZ]),
+    "pfm_prdc_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64, _I64]),
+    "pfm_prdc": (C.c_int, [_VP, _VP, _I64, _VP, _I64, _I64, _VP, _VP, _I64, _I64, _VP, _VP, _VP, _VP, _SZ]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -137,3 +140,26 @@ def wasserstein1d_status(p, cols, perm, gstart, ngroups, nr, nf, idx_r, idx_f, r
 
 def wasserstein1d(*args):
     check(wasserstein1d_status(*args), "pfm_wasserstein1d")
+
+
+def prdc_workspace_bytes(nr, nf, d, reps, k):
+    return int(lib().pfm_prdc_workspace_bytes(int(nr), int(nf), int(d), int(reps), int(k)))
+
+
+def prdc_status(Xr, Xf, idx_r, idx_f, reps, k, radius2_r, radius2_f, counts, ws):
+    """enqueue `reps` replicates of the k-nearest-neighbour counts on the current stream and return the status;
+    radius2_r / radius2_f are float64 views of reps * nr / reps * nf elements (the squared k-th-neighbour radii), counts an
+    int64 view of reps * 4 elements (P, Rc, Dn, Cv)"""
+    nr, d = Xr.shape
+    nf = Xf.shape[0]
+    assert Xf.shape[1] == d and idx_r.numel() == reps * nr and idx_f.numel() == reps * nf
+    assert radius2_r.numel() == reps * nr and radius2_f.numel() == reps * nf and counts.numel() == reps * 4
+    return int(lib().pfm_prdc(torch.cuda.current_stream().cuda_stream, _ptr(Xr, torch.float64, "X_real"), nr,
+                              _ptr(Xf, torch.float64, "X_fake"), nf, d, _ptr(idx_r, torch.int32, "idx_real"),
+                              _ptr(idx_f, torch.int32, "idx_fake"), int(reps), int(k),
+                              _ptr(radius2_r, torch.float64, "radius2_r"), _ptr(radius2_f, torch.float64, "radius2_f"),
+                              _ptr(counts, torch.int64, "counts"), _ptr(ws, torch.uint8, "workspace"), ws.numel()))
+
+
+def prdc(*args):
+    check(prdc_status(*args), "pfm_prdc")

@@ -14,6 +14,9 @@
  *   pfm_wasserstein1d the 1-D Wasserstein distance W_p^p (p = 1, 2) of every replicate's columns, from the
  *                     same sorted order and draw counts; pfm_project makes such columns of a
  *                     multivariate sample's projections (sliced Wasserstein distance)
+ *   pfm_prdc          k-nearest-neighbour precision, recall, density and coverage: every row's k-th-neighbour
+ *                     radius inside its own resampled set, then the real x fake squared distances against
+ *                     those radii, as four integer counts per replicate
  *
  * Conventions (as include/rnvp_hip.h)
  *   - every pointer is a DEVICE pointer; sizes are plain integers;
@@ -43,7 +46,8 @@ extern "C" {
 #define PFM_OK            0
 #define PFM_EINVAL       (-1)   /* NULL pointer, non-positive size, index range       */
 #define PFM_EUNSUPPORTED (-2)   /* d too large for the moments kernels' LDS row tile;
-                                   a Wasserstein order p other than 1 or 2              */
+                                   a Wasserstein order p other than 1 or 2;
+                                   nearest_k above PFM_KNN_MAX_K                         */
 #define PFM_EWORKSPACE   (-3)   /* workspace smaller than *_workspace_bytes() says      */
 
 #define PFM_VERSION 101         /* pfm_version(): bumped whenever an argument list changes */
@@ -140,6 +144,30 @@ size_t pfm_wasserstein1d_workspace_bytes(int64_t nr, int64_t nf, int64_t d, int6
 int pfm_wasserstein1d(void *stream, int p, const double *cols, const int32_t *perm, const int32_t *gstart,
                       const int32_t *ngroups, int64_t nr, int64_t nf, int64_t d, const int32_t *idx_r,
                       const int32_t *idx_f, int64_t reps, double *out, void *workspace, size_t workspace_bytes);
+
+/* ---- k-NN precision, recall, density, coverage (pf_knn.hip) ---------------------------------- */
+
+#define PFM_KNN_MAX_K 16        /* nearest_k: the per-thread candidate lists live in registers */
+
+/* bytes of workspace pfm_prdc needs (0: the arguments are invalid, k above PFM_KNN_MAX_K included, or a size overflows) */
+size_t pfm_prdc_workspace_bytes(int64_t nr, int64_t nf, int64_t d, int64_t reps, int64_t k);
+
+/*
+ * `reps` replicates of the k-nearest-neighbour counts behind improved precision / recall (Kynkaanniemi et al. 2019) and
+ * density / coverage (Naeem et al. 2020).  With R = Xr[idx_r[r]], F = Xf[idx_f[r]] and D2 the SQUARED Euclidean distance
+ * accumulated as fma(df, df, acc) over the features in order (no square root anywhere, no norm / dot-product identity):
+ *   radius2_r[r, i] = the (k + 1)-th smallest value of row i of D2(R, R), the diagonal 0 and the zeros of duplicated
+ *                     rows included (np.partition(row, k)[k]); radius2_f[r, j] the same inside F
+ *   c[j] = #{i : D2(R_i, F_j) < radius2_r[i]},  cov[i] = any_j D2(R_i, F_j) < radius2_r[i],
+ *   rec[i] = any_j D2(R_i, F_j) < radius2_f[j]                                  (strict <, as the prdc package)
+ *   counts[r] = { P = #{j : c[j] > 0}, Rc = #{i : rec[i]}, Dn = sum_j c[j], Cv = #{i : cov[i]} }
+ * precision = P / nf, recall = Rc / nr, density = Dn / (k nf), coverage = Cv / nr are left to the caller.
+ * radius2_r [reps, nr], radius2_f [reps, nf], counts [reps, 4].  PFM_EINVAL for k < 1 or k >= min(nr, nf),
+ * PFM_EUNSUPPORTED for k > PFM_KNN_MAX_K.
+ */
+int pfm_prdc(void *stream, const double *Xr, int64_t nr, const double *Xf, int64_t nf, int64_t d,
+             const int32_t *idx_r, const int32_t *idx_f, int64_t reps, int64_t k,
+             double *radius2_r, double *radius2_f, int64_t *counts, void *workspace, size_t workspace_bytes);
 
 #ifdef __cplusplus
 }
