@@ -17,7 +17,7 @@ MOMENTS_MAX_D = 4096       # PFM_MOMENTS_MAX_D
 M1D_KS, M1D_CVM, M1D_AD, M1D_AUC, M1D_HIST, M1D_KDE = range(6)
 CVM_MAX_N = 1 << 20        # pooled rows pfm_metric1d's Cramer-von Mises sums hold exactly
 KNN_MAX_K = 16             # PFM_KNN_MAX_K: the largest nearest_k of pfm_prdc
-PFM_EUNSUPPORTED, PFM_EWORKSPACE = -2, -3
+PFM_EINVAL, PFM_EUNSUPPORTED, PFM_EWORKSPACE = -1, -2, -3
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libpf_metrics.so")
@@ -61,30 +61,37 @@ def moments_workspace_bytes(nr, nf, d, reps):
     return int(lib().pfm_moments_workspace_bytes(int(nr), int(nf), int(d), int(reps)))
 
 
-def mmd(X, Y, idx_x, idx_y, reps, median, out, ws):
-    """enqueue `reps` MMD replicates on the current stream; idx_x / idx_y are flat int32 device views
-    [reps * nx] / [reps * ny]; median / out are float64 device views of `reps` elements"""
+def mmd_status(X, Y, idx_x, idx_y, reps, median, out, ws):
+    """enqueue `reps` MMD replicates on the current stream and return the status; idx_x / idx_y are flat int32 device
+    views [reps * nx] / [reps * ny]; median / out are float64 device views of `reps` elements"""
     nx, d = X.shape
     ny = Y.shape[0]
     assert idx_x.numel() == reps * nx and idx_y.numel() == reps * ny and median.numel() == reps == out.numel()
-    st = lib().pfm_mmd(torch.cuda.current_stream().cuda_stream, _ptr(X, torch.float64, "X"), nx, _ptr(Y, torch.float64, "Y"),
-                       ny, d, _ptr(idx_x, torch.int32, "idx_x"), _ptr(idx_y, torch.int32, "idx_y"), int(reps),
-                       _ptr(median, torch.float64, "median"), _ptr(out, torch.float64, "mmd"), _ptr(ws, torch.uint8, "workspace"),
-                       ws.numel())
-    check(st, "pfm_mmd")
+    return int(lib().pfm_mmd(torch.cuda.current_stream().cuda_stream, _ptr(X, torch.float64, "X"), nx,
+                             _ptr(Y, torch.float64, "Y"), ny, d, _ptr(idx_x, torch.int32, "idx_x"),
+                             _ptr(idx_y, torch.int32, "idx_y"), int(reps), _ptr(median, torch.float64, "median"),
+                             _ptr(out, torch.float64, "mmd"), _ptr(ws, torch.uint8, "workspace"), ws.numel()))
 
 
-def boot_moments(Xr, Xf, idx_r, idx_f, reps, mean, cov, ws):
-    """enqueue the bootstrap means [reps, 2, d] and covariances [reps, 2, d, d] on the current stream"""
+def mmd(*args):
+    check(mmd_status(*args), "pfm_mmd")
+
+
+def boot_moments_status(Xr, Xf, idx_r, idx_f, reps, mean, cov, ws):
+    """enqueue the bootstrap means [reps, 2, d] and covariances [reps, 2, d, d] on the current stream and return the
+    status"""
     nr, d = Xr.shape
     nf = Xf.shape[0]
     assert idx_r.numel() == reps * nr and idx_f.numel() == reps * nf
     assert mean.numel() == reps * 2 * d and cov.numel() == reps * 2 * d * d
-    st = lib().pfm_boot_moments(torch.cuda.current_stream().cuda_stream, _ptr(Xr, torch.float64, "X_real"), nr,
-                                _ptr(Xf, torch.float64, "X_fake"), nf, d, _ptr(idx_r, torch.int32, "idx_real"),
-                                _ptr(idx_f, torch.int32, "idx_fake"), int(reps), _ptr(mean, torch.float64, "mean"),
-                                _ptr(cov, torch.float64, "cov"), _ptr(ws, torch.uint8, "workspace"), ws.numel())
-    check(st, "pfm_boot_moments")
+    return int(lib().pfm_boot_moments(torch.cuda.current_stream().cuda_stream, _ptr(Xr, torch.float64, "X_real"), nr,
+                                      _ptr(Xf, torch.float64, "X_fake"), nf, d, _ptr(idx_r, torch.int32, "idx_real"),
+                                      _ptr(idx_f, torch.int32, "idx_fake"), int(reps), _ptr(mean, torch.float64, "mean"),
+                                      _ptr(cov, torch.float64, "cov"), _ptr(ws, torch.uint8, "workspace"), ws.numel()))
+
+
+def boot_moments(*args):
+    check(boot_moments_status(*args), "pfm_boot_moments")
 
 
 def metric1d_workspace_bytes(metric, nr, nf, d, reps, bins):

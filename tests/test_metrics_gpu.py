@@ -1,6 +1,14 @@
 """probaforms_amd.metrics on the GPU: the HIP kernels of libpf_metrics.so against the reference's committed
 fixtures (tests/golden/metrics_*.npz), an independent float64 numpy restatement (tests/metrics_numpy.py)
-on shapes the fixtures do not cover, the global RNG state, bitwise reproducibility and CUDA-tensor inputs."""
+on shapes the fixtures do not cover, the global RNG state, bitwise reproducibility and CUDA-tensor inputs.
+
+The shapes here (nx, ny, d): MMD (50, 51, 3), (60, 70, 100), (129, 65, 5), (1, 2, 2), (4000, 4000, 16); moments (50, 51, 3),
+(40, 70, 100), (3000, 2500, 1), (5000, 4100, 16), all continuous Gaussian data through the public path.  The edges of the kernels are
+in tests/test_metrics_edges_gpu.py, through the raw entry points: the median select where the two middle keys part in each of its
+six digits, tie exactly, or straddle the diagonal zeros; dyadic data with bitwise medians; replicates of different kinds in one call;
+MMD seam and feature-chunk shapes (64, 64, 16), (63, 66, 17), (1, 130, 32), (130, 1, 33), (65, 1, 1); moments with unequal and
+saturated row parts (2048 | 2049, 4097 | 100, 133122 rows), d = 2, 3, 22, 23, 65, 257, 2049, one- and two-row samples, samples
+centred at +-1e6; the status codes on poisoned outputs."""
 import glob
 import os
 import sys

@@ -1,5 +1,6 @@
 """probaforms_amd.metrics without a GPU: the bootstrap index stream, the host trace-sqrtm, the committed
-reference fixtures against the float64 restatement, argument checks, and the probaforms.metrics alias."""
+reference fixtures against the float64 restatement, argument checks, the probaforms.metrics alias, and the proof that every
+constructed input of tests/metrics_cases.py has the property tests/test_metrics_edges_gpu.py relies on."""
 import glob
 import os
 import subprocess
@@ -12,6 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 sys.path.insert(0, ROOT)
 
+import metrics_cases as mc  # noqa: E402
 import metrics_numpy as mn  # noqa: E402
 from probaforms_amd.metrics import _boot  # noqa: E402
 from probaforms_amd.metrics.fd import trace_sqrtm  # noqa: E402
@@ -177,3 +179,85 @@ def test_install_as_probaforms_exposes_exactly_the_two_metrics():
              "    print('ok')\n"
              "from probaforms.models import RealNVP\n")
     assert r.returncode == 0 and "ok" in r.stdout, r.stderr
+
+
+# ---- tests/metrics_cases.py: every constructed input has its named property, from the numpy restatement alone -------------------
+
+def test_key_digits_are_the_kernels_layout():
+    assert mc.SHIFT[0] + mc.WIDTH[0] == 64 and mc.SHIFT[-1] == 0
+    assert all(mc.SHIFT[i] == mc.SHIFT[i + 1] + mc.WIDTH[i + 1] for i in range(5))
+    assert mc.key(0.0) == 0 and mc.key(5e-324) == 1 and mc.key(1.0) == 0x3FF << 52
+    assert mc.parting_digit(1.0, 1.0) is None and mc.parting_digit(1.0, 2.0) == 0
+    assert [mc.parting_digit(0.0, np.float64(2.0 ** (s - 1074))) for s in mc.SHIFT[1:]] == [1, 2, 3, 4, 5]
+
+
+@pytest.mark.parametrize("digit", sorted(mc.PARTING))
+def test_four_points_part_the_middle_keys_in_the_named_digit(digit):
+    X, Y = mc.four_points(*mc.PARTING[digit])
+    Z = np.concatenate((X, Y))
+    lo, hi = mc.middle_values(Z)
+    assert 0 < lo < hi and mc.parting_digit(lo, hi) == digit
+    # both middle values are exact (so the kernel's fma chain and the restatement's products and sums give the same bits), and
+    # they are the 2nd and 3rd smallest pair (in the digit-0 case two pairs share the upper one)
+    u = np.sort(mn.pooled_upper_d2(Z))
+    Zl = Z.astype(np.longdouble)
+    ul = np.sort(np.array([((Zl[i] - Zl[j]) ** 2).sum() for i in range(4) for j in range(i + 1, 4)]))
+    assert u[1] == lo and u[2] == hi and u[0] < lo and hi <= u[3]
+    assert np.longdouble(lo) == ul[1] and np.longdouble(hi) == ul[2]
+    assert mn.median_distance(Z) == (np.sqrt(lo) + np.sqrt(hi)) / 2
+
+
+def test_four_points_tie_has_equal_middle_keys():
+    X, Y = mc.four_points(*mc.TIE)
+    Z = np.concatenate((X, Y))
+    lo, hi = mc.middle_values(Z)
+    assert (len(Z) ** 2) % 2 == 0 and lo > 0
+    assert mc.key(lo) == mc.key(hi) and mc.parting_digit(lo, hi) is None
+    u = np.sort(mn.pooled_upper_d2(Z))
+    assert u[0] < u[1] == u[2] == lo < u[3]                       # two different pairs share the bits: ranks 6 to 9
+    Zl = Z.astype(np.longdouble)
+    assert ((Zl[1] - Zl[3]) ** 2).sum() == np.longdouble(lo) == ((Zl[2] - Zl[3]) ** 2).sum()       # and they are exact
+
+
+@pytest.mark.parametrize("digit", sorted(mc.LADDER))
+def test_ladder_parts_a_diagonal_zero_from_the_pair_in_the_named_digit(digit):
+    X, Y = mc.ladder(mc.LADDER[digit])
+    Z = np.concatenate((X, Y))
+    lo, hi = mc.middle_values(Z)
+    assert lo == 0.0 and hi > 0 and mc.parting_digit(lo, hi) == digit
+    assert all(g == 0 for g in mc.digits(hi)[:digit])             # the pair shares the all-zero prefix up to that digit
+    if digit == 0:
+        assert hi == 2.25
+    else:                                                     # d^2 is the denormal with the integer key k^2: exact
+        k = mc.LADDER[digit] / 2.0 ** -537
+        assert mc.key(hi) == int(k) ** 2 and np.sqrt(hi) == mc.LADDER[digit]
+    assert mn.median_distance(Z) == mc.LADDER[digit] / 2
+
+
+def test_dyadic_case_is_exact_and_tied_at_the_middle():
+    X, Y, idx = mc.dyadic()
+    assert (X.shape[0], Y.shape[0], X.shape[1]) == mc.DYADIC_SHAPE and len(idx) == mc.DYADIC_REPS
+    assert ((X.shape[0] + Y.shape[0]) ** 2) % 2 == 0
+    for ix, iy in idx:
+        Z = np.concatenate((X[ix], Y[iy]))
+        u = mn.pooled_upper_d2(Z)
+        Zl = Z.astype(np.longdouble)
+        m = len(Z)
+        ul = np.concatenate([((Zl[i + 1:] - Zl[i]) ** 2).sum(axis=1) for i in range(m - 1)])
+        assert ul.dtype == np.longdouble and np.array_equal(u.astype(np.longdouble), ul)       # every d^2 is exact
+        for v in mc.middle_values(Z):
+            shared = int((u == v).sum())
+            print("middle d^2 %r: %d pairs, %d entries of the full matrix" % (v, shared, 2 * shared))
+            assert v > 0 and shared >= 2                          # at least two different pairs: a tie the select must hold
+
+
+def test_moments_longdouble_agrees_with_numpy():
+    rng = np.random.default_rng(0)
+    B = rng.normal(size=(40, 5)) * rng.uniform(0.5, 2, 5) + 3.0
+    mean, cov = mc.moments_longdouble(B)
+    assert mean.dtype == np.longdouble and cov.dtype == np.longdouble
+    np.testing.assert_allclose(mean.astype(np.float64), B.mean(axis=0), rtol=1e-13, atol=0)
+    np.testing.assert_allclose(cov.astype(np.float64), np.cov(B, rowvar=False), rtol=1e-13, atol=1e-13)
+    assert np.array_equal(cov, cov.T)
+    one = mc.moments_longdouble(B[:1])
+    assert np.array_equal(one[0].astype(np.float64), B[0]) and np.isnan(one[1]).all()
