@@ -18,15 +18,21 @@ def groups(x, y):
     return vals, l, a, np.cumsum(l) - l, np.cumsum(a) - a
 
 
-def ks(x, y):
-    """ks_2samp's statistic: the largest cdf difference at the pooled values; scipy's exact method (both samples of
-    at most 10 000 rows) then returns it as the fraction h / lcm(nx, ny), h = round(d * lcm)"""
+def ks_raw(x, y):
+    """the largest cdf difference at the pooled values, before ks_2samp's h / lcm step: what the kernel returns"""
     nx, ny = len(x), len(y)
     _, l, a, C, Cr = groups(x, y)
     diff = (Cr + a) / nx - ((C + l) - (Cr + a)) / ny
     minS = np.clip(-np.min(diff), 0, 1)
     maxS = np.max(diff)
-    d = minS if minS > maxS else maxS
+    return minS if minS > maxS else maxS
+
+
+def ks(x, y):
+    """ks_2samp's statistic: ks_raw; scipy's exact method (both samples of at most 10 000 rows) then returns it as the
+    fraction h / lcm(nx, ny), h = round(d * lcm)"""
+    nx, ny = len(x), len(y)
+    d = ks_raw(x, y)
     if max(nx, ny) > 10000:
         return d
     lcm = (nx // math.gcd(nx, ny)) * ny
@@ -58,29 +64,48 @@ def cvm(x, y):
     return u / (k * N) - (4 * k - 1) / (6 * N)
 
 
+def auc_u2(x, y):
+    """2 U, U the Mann-Whitney statistic of the fake rows (a tie counts 1/2): an exact integer"""
+    _, l, a, C, Cr = groups(x, y)
+    return int(np.sum((l - a) * (2 * Cr + a)))
+
+
 def auc(x, y):
     """|roc_auc_score([0] * nx + [1] * ny, [x; y]) - 0.5| + 0.5 = |U / (nx ny) - 0.5| + 0.5"""
-    _, l, a, C, Cr = groups(x, y)
-    u2 = int(np.sum((l - a) * (2 * Cr + a)))
+    u2 = auc_u2(x, y)
     v = (u2 / 2.0) / (len(x) * len(y))
     return abs(v - 0.5) + 0.5
 
 
-def ad(x, y):
-    """anderson_ksamp([x, y]).statistic, midrank, in scipy's per-value operation order"""
+def ad_sums(x, y):
+    """-> (sum_r, sum_f, distinct): scipy's _anderson_ksamp_midrank `inner` summed over the distinct pooled values for
+    the real and for the fake sample, in scipy's per-value operation order, and the number of distinct values (with a
+    single one `inner` is 0 / 0)"""
     _, l, a, C, Cr = groups(x, y)
-    if len(l) < 2:
-        raise ValueError("one distinct value")
     n = np.array([len(x), len(y)])
     N = int(n.sum())
     lj = l.astype(np.float64)
     Bj = C + lj / 2.
-    A2akN = 0.
+    sums = []
     for i, (cnt, below) in enumerate(((a, Cr), (l - a, C - Cr))):
         Mij = (below + cnt).astype(float)
         Mij -= cnt / 2.
-        inner = lj / float(N) * (N * Mij - Bj * n[i]) ** 2 / (Bj * (N - Bj) - N * l / 4.)
-        A2akN += inner.sum() / n[i]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            inner = lj / float(N) * (N * Mij - Bj * n[i]) ** 2 / (Bj * (N - Bj) - N * l / 4.)
+        sums.append(inner.sum())
+    return sums[0], sums[1], len(l)
+
+
+def ad(x, y):
+    """anderson_ksamp([x, y]).statistic, midrank, in scipy's per-value operation order"""
+    sr, sf, distinct = ad_sums(x, y)
+    if distinct < 2:
+        raise ValueError("one distinct value")
+    n = np.array([len(x), len(y)])
+    N = int(n.sum())
+    A2akN = 0.
+    A2akN += sr / n[0]
+    A2akN += sf / n[1]
     A2akN *= (N - 1.) / N
     k = 2
     H = (1. / n).sum()
@@ -125,14 +150,19 @@ def hist_div(x, y, bins, js):
         return (js_divergence if js else kl_divergence)(p + eps, q + eps)
 
 
-def kde_probs(s, grid):
-    """exp(KernelDensity(bandwidth='silverman').fit(s).score_samples(grid)) normalised: a max-shifted log-sum-exp
-    of the Gaussian log kernel, plus its norm, minus log n"""
-    n = len(s)
-    h = (n * 3 / 4) ** (-1 / 5)
+def kde_logsum(s, grid, h):
+    """log sum_i exp(-0.5 (grid_k - s_i)^2 / h^2) per grid point, shifted by its largest term: what the kernel returns"""
     t = -0.5 * (grid[:, None] - s[None, :]) ** 2 / (h * h)
     m = t.max(axis=1)
-    lse = m + np.log(np.exp(t - m[:, None]).sum(axis=1))
+    return m + np.log(np.exp(t - m[:, None]).sum(axis=1))
+
+
+def kde_probs(s, grid):
+    """exp(KernelDensity(bandwidth='silverman').fit(s).score_samples(grid)) normalised: kde_logsum plus the Gaussian
+    norm, minus log n"""
+    n = len(s)
+    h = (n * 3 / 4) ** (-1 / 5)
+    lse = kde_logsum(s, grid, h)
     with np.errstate(divide="ignore", invalid="ignore", under="ignore"):
         p = np.exp(lse + (-0.5 * math.log(2 * math.pi) - math.log(h)) - np.log(n))
         return p / p.sum()
