@@ -18,10 +18,11 @@ The eight 1-D metrics of the reference live in the reference's module paths, not
 
 The metrics the reference does not have are modules of their own, outside the export list as well: the Wasserstein distances
 (wasserstein.py) and k-nearest-neighbour precision, recall, density and coverage, which say in which way a generated sample is
-wrong (fidelity against diversity) where the distances only say how much:
+wrong (fidelity against diversity) where the distances only say how much, and the parameter-free energy distance:
 
     from probaforms_amd.metrics.wasserstein import wasserstein_1d, sliced_wasserstein_distance
     from probaforms_amd.metrics.prdc import prdc, prdc_full_sample     # bootstrapped (mean, std) pairs; the samples as given
+    from probaforms_amd.metrics.energy import energy_distance, energy_distance_full_sample
 
 `__all__` and the `probaforms.metrics` alias (`probaforms_amd.install_as_probaforms()`) name only the two
 multivariate metrics, so `from probaforms.metrics import kolmogorov_smirnov_1d` raises ImportError there.

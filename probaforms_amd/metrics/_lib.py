@@ -17,6 +17,8 @@ MOMENTS_MAX_D = 4096       # PFM_MOMENTS_MAX_D
 M1D_KS, M1D_CVM, M1D_AD, M1D_AUC, M1D_HIST, M1D_KDE = range(6)
 CVM_MAX_N = 1 << 20        # pooled rows pfm_metric1d's Cramer-von Mises sums hold exactly
 KNN_MAX_K = 16             # PFM_KNN_MAX_K: the largest nearest_k of pfm_prdc
+ENERGY_TILE = 64           # PFM_ENERGY_TILE: rows per side of a pair tile of pfm_energy
+ENERGY_REP_BLOCK = 16      # PFM_ENERGY_REP_BLOCK: replicates per count tile of pfm_energy
 PFM_EINVAL, PFM_EUNSUPPORTED, PFM_EWORKSPACE = -1, -2, -3
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -39,6 +41,8 @@ _SIGNATURES = {
     "pfm_wasserstein1d": (C.c_int, [_VP, C.c_int, _VP, _VP, _VP, _VP, _I64, _I64, _I64, _VP, _VP, _I64, _VP, _VP, _SZ]),
     "pfm_prdc_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64, _I64]),
     "pfm_prdc": (C.c_int, [_VP, _VP, _I64, _VP, _I64, _I64, _VP, _VP, _I64, _I64, _VP, _VP, _VP, _VP, _SZ]),
+    "pfm_energy_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64]),
+    "pfm_energy": (C.c_int, [_VP, _VP, _I64, _VP, _I64, _I64, _VP, _VP, _I64, _VP, _VP, _SZ]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -170,3 +174,23 @@ def prdc_status(Xr, Xf, idx_r, idx_f, reps, k, radius2_r, radius2_f, counts, ws)
 
 def prdc(*args):
     check(prdc_status(*args), "pfm_prdc")
+
+
+def energy_workspace_bytes(nr, nf, d, reps):
+    return int(lib().pfm_energy_workspace_bytes(int(nr), int(nf), int(d), int(reps)))
+
+
+def energy_status(Xr, Xf, idx_r, idx_f, reps, sums, ws):
+    """enqueue `reps` replicates of the energy distance's three raw pair sums on the current stream and return the status;
+    sums is a float64 view of reps * 3 elements (Srr, Sff, Srf)"""
+    nr, d = Xr.shape
+    nf = Xf.shape[0]
+    assert Xf.shape[1] == d and idx_r.numel() == reps * nr and idx_f.numel() == reps * nf and sums.numel() == reps * 3
+    return int(lib().pfm_energy(torch.cuda.current_stream().cuda_stream, _ptr(Xr, torch.float64, "X_real"), nr,
+                                _ptr(Xf, torch.float64, "X_fake"), nf, d, _ptr(idx_r, torch.int32, "idx_real"),
+                                _ptr(idx_f, torch.int32, "idx_fake"), int(reps), _ptr(sums, torch.float64, "sums"),
+                                _ptr(ws, torch.uint8, "workspace"), ws.numel()))
+
+
+def energy(*args):
+    check(energy_status(*args), "pfm_energy")

@@ -17,6 +17,9 @@
  *   pfm_prdc          k-nearest-neighbour precision, recall, density and coverage: every row's k-th-neighbour
  *                     radius inside its own resampled set, then the real x fake squared distances against
  *                     those radii, as four integer counts per replicate
+ *   pfm_energy        the energy distance's three pair sums (real x real, fake x fake, real x fake Euclidean
+ *                     distances) of every replicate: each distance is formed once per call on the original rows
+ *                     and weighted by the replicates' draw counts, one float64 multiply-add per replicate and pair
  *
  * Conventions (as include/rnvp_hip.h)
  *   - every pointer is a DEVICE pointer; sizes are plain integers;
@@ -168,6 +171,29 @@ size_t pfm_prdc_workspace_bytes(int64_t nr, int64_t nf, int64_t d, int64_t reps,
 int pfm_prdc(void *stream, const double *Xr, int64_t nr, const double *Xf, int64_t nf, int64_t d,
              const int32_t *idx_r, const int32_t *idx_f, int64_t reps, int64_t k,
              double *radius2_r, double *radius2_f, int64_t *counts, void *workspace, size_t workspace_bytes);
+
+/* ---- energy distance (pf_energy.hip) ----------------------------------------------------------- */
+
+#define PFM_ENERGY_TILE 64      /* rows per side of a pair tile: a tile lies inside one of the blocks RR, FF, RF */
+#define PFM_ENERGY_REP_BLOCK 16 /* replicates whose draw counts are staged and multiplied at a time */
+
+/* bytes of workspace pfm_energy needs: the draw counts and the workgroups' partial sums (0: the arguments are invalid or a
+   size overflows) */
+size_t pfm_energy_workspace_bytes(int64_t nr, int64_t nf, int64_t d, int64_t reps);
+
+/*
+ * `reps` replicates of the three raw pair sums of the energy distance (Szekely & Rizzo), V-statistic: with R = Xr[idx_r[r]],
+ * F = Xf[idx_f[r]] and |.| the Euclidean norm, the squared distance accumulated as fma(df, df, acc) over the features in
+ * order and one sqrt (no norm / dot-product identity: duplicated rows are at distance exactly 0),
+ *   sums[r] = { Srr = sum_a sum_b |R_a - R_b|,  Sff = sum_a sum_b |F_a - F_b|,  Srf = sum_a sum_b |R_a - F_b| }
+ * over all ordered pairs, the zero diagonals of Srr and Sff included.  D^2 = 2 Srf / (nr nf) - Srr / nr^2 - Sff / nf^2 is
+ * left to the caller.  Computed as sum_ab c[a] c[b] |z_a - z_b| over the ORIGINAL rows with the replicate's draw counts c;
+ * the order of summation depends on (nr, nf) only, so a replicate's sums are bitwise the same in any call.  Every element
+ * of sums [reps, 3] is written.
+ */
+int pfm_energy(void *stream, const double *Xr, int64_t nr, const double *Xf, int64_t nf, int64_t d,
+               const int32_t *idx_r, const int32_t *idx_f, int64_t reps, double *sums, void *workspace,
+               size_t workspace_bytes);
 
 #ifdef __cplusplus
 }
