@@ -180,12 +180,43 @@ __device__ __forceinline__ void build_bin(const float (&xr)[R][2 * NF], const fl
 
 __device__ __forceinline__ f4 lds_f4(const uint32_t *p) { return *reinterpret_cast<const f4 *>(p); }
 
+// a fragment of the direct form: wave-uniform base (kept in an SGPR pair) + the lane's 32-bit dword offset, so that the load needs
+// no address arithmetic on the VALU
+typedef const __attribute__((address_space(1))) uint32_t *gu32_ptr;
+__device__ __forceinline__ gu32_ptr sbase(const uint32_t *p) {
+    asm volatile("" : "+s"(p));          // opaque and scalar: the base stays in SGPRs and the load stays where it is written
+    return (gu32_ptr)p;
+}
+__device__ __forceinline__ f4 gl_f4(gu32_ptr base, unsigned off) { return *reinterpret_cast<const __attribute__((address_space(1))) f4 *>(base + off); }
+
+// Direct form: the fragments a stage needs before its tile loop runs -- both operands of the first tile, GEMM1's of the second --
+// requested during the LAST tile of the stage before (prefetch_stage), so that they travel under that tile's activation and GEMM2
+// and, between two layers, under the reduce-scatter and the affine update instead of in front of an idle wave.
+template <int NI, int NA2> struct StagePre { f4 a1c[NI], b1c, a2c[NA2], a1n[NI], b1n; };
+
+template <int NI, int NA2>
+__device__ __forceinline__ void prefetch_stage(const uint32_t *sb, const Geo3 &g, int lane, int ntiles, StagePre<NI, NA2> &p) {
+    const int q = lane >> 4, t1 = ntiles > 1 ? 1 : 0;
+    const gu32_ptr g0 = sbase(sb), g2 = sbase(sb + NI * 256), g1 = sbase(sb + t1 * g.tile_dw);
+    const gu32_ptr gb = sbase(sb + g.TC * g.tile_dw), gbn = sbase(sb + g.TC * g.tile_dw + t1 * 16);
+#pragma unroll
+    for (int i = 0; i < NI; ++i) p.a1c[i] = gl_f4(g0, lane * 4 + i * 256);
+    p.b1c = gl_f4(gb, q * 4);
+#pragma unroll
+    for (int o = 0; o < NA2; ++o) p.a2c[o] = gl_f4(g2, lane * 4 + o * 256);
+#pragma unroll
+    for (int i = 0; i < NI; ++i) p.a1n[i] = gl_f4(g1, lane * 4 + i * 256);
+    p.b1n = gl_f4(gbn, q * 4);
+}
+
 // One stage (ntiles hidden tiles of net NET) from the LDS image `sb`.  Software pipeline as rnvp_mfma_layer.h:
 // GEMM1 of tile t+1 issues while the activation of tile t runs on the VALU; fragments come from LDS one tile ahead.
 // X4 (NF == 2): GEMM2 as 16 independent 4x4x1 blocks into outx[rt][2*NET + o]; otherwise 16x16x4 into out[rt][NET*OTL + o].
-template <int NF, int CQ, int R, int NET, int ACT, int NOUT>
+template <int NF, int CQ, int R, int NET, int ACT, int NOUT, bool GL = false>
 __device__ __forceinline__ void run_stage(const uint32_t *sb, const Geo3 &g, int lane, int ntiles,
-                                          const f4 (&bin)[R][D3<NF, CQ>::NI], f4 (&out)[R][NOUT]) {
+                                          const f4 (&bin)[R][D3<NF, CQ>::NI], f4 (&out)[R][NOUT],
+                                          StagePre<D3<NF, CQ>::NI, D3<NF, CQ>::NA2> *pre = nullptr, const uint32_t *next_sb = nullptr,
+                                          int next_ntiles = 0) {
     using D = D3<NF, CQ>;
     constexpr int NI = D::NI, NA2 = D::NA2, OTL = D::OTL;
     constexpr bool X4 = NF == 2;
@@ -242,7 +273,15 @@ __device__ __forceinline__ void run_stage(const uint32_t *sb, const Geo3 &g, int
         return;
     }
     St s0, s1;
-    {
+    if constexpr (GL) {                     // GL: the direct form, fragments from global memory; this stage's head is in *pre
+#pragma unroll
+        for (int o = 0; o < NA2; ++o) s0.a2c[o] = pre->a2c[o];
+#pragma unroll
+        for (int i = 0; i < NI; ++i) s0.a1n[i] = pre->a1n[i];
+        s0.b1n = pre->b1n;
+#pragma unroll
+        for (int rt = 0; rt < R; ++rt) s0.acc[rt] = gemm1(pre->a1c, pre->b1c, rt);
+    } else {
         f4 a1c[NI], b1c;
 #pragma unroll
         for (int i = 0; i < NI; ++i) a1c[i] = lds_f4(pT + i * 256);
@@ -259,11 +298,15 @@ __device__ __forceinline__ void run_stage(const uint32_t *sb, const Geo3 &g, int
     auto gemm2 = [&](const St &c, const f4 (&hv)[R]) {
         if constexpr (X4) {
 #pragma unroll
-            for (int rho = 0; rho < 4; ++rho)
+            for (int rho = 0; rho < 4; ++rho) {
+                // direct form: keep the written order (every accumulator comes round again after 2 R - 1 others); left alone the
+                // scheduler walks the accumulators back and forth and pays a wait state at every turn
+                if constexpr (GL) { if (rho) __builtin_amdgcn_sched_barrier(0); }
 #pragma unroll
                 for (int o = 0; o < 2; ++o)
 #pragma unroll
                     for (int rt = 0; rt < R; ++rt) out[rt][2 * NET + o] = mfma::mfma4(c.a2c[o][rho], hv[rt][rho], out[rt][2 * NET + o]);
+            }
         } else {
 #pragma unroll
             for (int o = 0; o < OTL; ++o)
@@ -276,11 +319,20 @@ __device__ __forceinline__ void run_stage(const uint32_t *sb, const Geo3 &g, int
     };
     auto step = [&](const St &c, St &nx, int t) {
         const int t2 = (t + 2 < last) ? t + 2 : last;
+        if constexpr (GL) {
+            const gu32_ptr g1 = sbase(sb + t2 * tdw), gb = sbase(sb + g.TC * tdw + t2 * 16), g2 = sbase(sb + (t + 1) * tdw + NI * 256);
+#pragma unroll
+            for (int i = 0; i < NI; ++i) nx.a1n[i] = gl_f4(g1, lane * 4 + i * 256);
+            nx.b1n = gl_f4(gb, q * 4);
+#pragma unroll
+            for (int o = 0; o < NA2; ++o) nx.a2c[o] = gl_f4(g2, lane * 4 + o * 256);
+        } else {
 #pragma unroll
         for (int i = 0; i < NI; ++i) nx.a1n[i] = lds_f4(pT + t2 * tdw + i * 256);
         nx.b1n = lds_f4(pB1 + t2 * 16);
 #pragma unroll
         for (int o = 0; o < NA2; ++o) nx.a2c[o] = lds_f4(pT + (t + 1) * tdw + (NI + o) * 256);
+        }
         __builtin_amdgcn_sched_barrier(0);
         f4 hv[R];
 #pragma unroll
@@ -292,6 +344,10 @@ __device__ __forceinline__ void run_stage(const uint32_t *sb, const Geo3 &g, int
         __builtin_amdgcn_sched_barrier(0);
     };
     auto finish = [&](const St &c) {
+        if constexpr (GL) {
+            prefetch_stage(next_sb, g, lane, next_ntiles, *pre);
+            __builtin_amdgcn_sched_barrier(0);
+        }
         f4 hv[R];
 #pragma unroll
         for (int rt = 0; rt < R; ++rt) hv[rt] = mfma::act4<ACT>(c.acc[rt]);
@@ -324,7 +380,10 @@ __device__ __attribute__((noinline)) f4 prior_normal4_cold(uint64_t seed, int64_
 
 // STAGED: the workgroup's WAVES waves share each stage through LDS (above).  !STAGED (d <= 16, where a stage is small and
 // the barrier-paced schedule loses more than the shared copy saves): every wave reads the same stage images straight from
-// global memory, one hidden tile ahead, like the f32 kernels of rnvp_mfma_layer.h -- no LDS, no barriers.
+// global memory, one hidden tile ahead, like the f32 kernels of rnvp_mfma_layer.h -- no LDS, no barriers.  Its pipeline runs
+// across stage, layer and row-group boundaries (StagePre), its fragment loads take scalar bases (sbase), and its layers are an
+// explicit loop with the features kept by role, so that the accumulators die in the reduce-scatter and no layer selects registers by
+// its mask parity: 256 -> 221 ... 235 VGPRs, no scratch (profiles/r07_flow_seams_ab.txt).
 template <int NF, int CQ, int R, bool INVERSE, int ACT, int WAVES, bool STAGED>
 __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(RNVP_WPE, RNVP_WPE)))
 k_flow_bx3(const uint32_t *__restrict__ wp, Geo3 g, int L, int alt, const float *x, const float *__restrict__ c,
@@ -334,6 +393,7 @@ k_flow_bx3(const uint32_t *__restrict__ wp, Geo3 g, int L, int alt, const float 
     constexpr int DD = 8 * NF, CD = 4 * CQ, NI = D::NI, OTL = D::OTL, NT2 = D::NT2;
     constexpr bool X4 = NF == 2;
     constexpr int NOUT = X4 ? 4 : NT2;
+    static_assert(STAGED || X4, "the direct form exists for NF == 2 only");
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];       // two stage buffers of g.SD dwords
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     // known uniform: row bases in SGPRs
     const int q = lane >> 4, r = lane & 15;
@@ -351,6 +411,7 @@ k_flow_bx3(const uint32_t *__restrict__ wp, Geo3 g, int L, int alt, const float 
         return wp + ((size_t)l * 2 * g.NCH + rem) * g.SD;
     };
     float wave_sum = 0.f;
+    [[maybe_unused]] StagePre<NI, D::NA2> pre;         // direct form: the head of the next stage, carried across stages, layers and row groups
     if constexpr (STAGED) {
         if ((int64_t)blockIdx.x < ngroups) issue_stage<WAVES>(stage_src(0), lds, g.NP, wave, lane);
     }
@@ -378,6 +439,85 @@ k_flow_bx3(const uint32_t *__restrict__ wp, Geo3 g, int L, int alt, const float 
         const bool more = grp + gridDim.x < ngroups; (void)more;
         f4 bin[R][NI];
         f4 out[R][NOUT];
+        if constexpr (!STAGED && X4) {
+            auto chunk_nt = [&](int ch) { return (g.HT - ch * g.TC) < g.TC ? (g.HT - ch * g.TC) : g.TC; };
+            const size_t layer_dw = (size_t)2 * g.NCH * g.SD;
+            if (grp == (int64_t)blockIdx.x) prefetch_stage(stage_src(0), g, lane, chunk_nt(0), pre);      // later row groups: by the last stage
+            // one explicit loop over the layers: the accumulators are born at the layer's head and die in its reduce-scatter, so the
+            // lane swaps run in place (in the stage loop below they stay live around the loop and every swap works on a copy)
+            // the features by ROLE, not by position: xc conditions this layer and xt is transformed by it; the roles swap after every
+            // layer (alternating masks), so no layer selects registers by its parity
+            float xc[R][NF], xt[R][NF];
+            {
+                const int pc0 = ((INVERSE ? L - 1 : 0) + alt) & 1;
+#pragma unroll
+                for (int rt = 0; rt < R; ++rt)
+#pragma unroll
+                    for (int f = 0; f < NF; ++f) {
+                        xc[rt][f] = pc0 ? xr[rt][2 * f + 1] : xr[rt][2 * f];
+                        xt[rt][f] = pc0 ? xr[rt][2 * f] : xr[rt][2 * f + 1];
+                    }
+            }
+            for (int lp = 0; lp < L; ++lp) {
+                const int l = INVERSE ? L - 1 - lp : lp;
+                if constexpr (CQ > 0) {
+                    // the conditions' bf16 terms are the same in every layer: left alone, the compiler computes them once per row
+                    // group, finds no register for them and parks them in scratch (written through to HBM, re-read per layer);
+                    // 7 VALU operations per value and layer instead
+#pragma unroll
+                    for (int rt = 0; rt < R; ++rt)
+#pragma unroll
+                        for (int u = 0; u < CQ; ++u) asm volatile("" : "+v"(cr[rt][u]));
+                }
+                {
+                    float xin[R][2 * NF];
+#pragma unroll
+                    for (int rt = 0; rt < R; ++rt)
+#pragma unroll
+                        for (int f = 0; f < NF; ++f) { xin[rt][2 * f] = xc[rt][f]; xin[rt][2 * f + 1] = 0.f; }
+                    build_bin<NF, CQ, 0, R>(xin, cr, bin);
+                }
+#pragma unroll
+                for (int rt = 0; rt < R; ++rt)
+#pragma unroll
+                    for (int u = 0; u < NOUT; ++u) out[rt][u] = f4{0.f, 0.f, 0.f, 0.f};
+                // every stage requests the head of the one after it (the stages of a layer lie one behind the other); the last of a
+                // layer that of the next layer's first, the last of a row group that of the pass's first
+                const int ln = lp + 1 < L ? (INVERSE ? l - 1 : l + 1) : (INVERSE ? L - 1 : 0);
+                const uint32_t *sl = wp + (size_t)l * layer_dw;
+                for (int ch = 0; ch < g.NCH; ++ch, sl += g.SD)
+                    run_stage<NF, CQ, R, 0, ACT, NOUT, true>(sl, g, lane, chunk_nt(ch), bin, out, &pre, sl + g.SD, chunk_nt(ch + 1 < g.NCH ? ch + 1 : 0));
+                for (int ch = 0; ch < g.NCH; ++ch, sl += g.SD)
+                    run_stage<NF, CQ, R, 1, ACT, NOUT, true>(sl, g, lane, chunk_nt(ch), bin, out, &pre,
+                                                             ch + 1 < g.NCH ? sl + g.SD : wp + (size_t)ln * layer_dw, chunk_nt(ch + 1 < g.NCH ? ch + 1 : 0));
+                const f4 bias2 = *reinterpret_cast<const f4 *>(b2base + (size_t)l * g.b2_floats + q * 4);
+#pragma unroll
+                for (int rt = 0; rt < R; ++rt) {
+                    float tv[2], sv[2];
+                    mfma::reduce_scatter_x4(out[rt], tv, sv);
+                    const float tvv[2] = {tv[0] + bias2[0], tv[1] + bias2[1]}, svv[2] = {sv[0] + bias2[2], sv[1] + bias2[3]};
+#pragma unroll
+                    for (int f = 0; f < NF; ++f) {
+                        const float xv = xt[rt][f];
+                        float nv;
+                        if (INVERSE) nv = (xv - tvv[f]) * expf(-svv[f]);
+                        else { nv = fmaf(xv, expf(svv[f]), tvv[f]); ld[rt] += svv[f]; }
+                        xt[rt][f] = xc[rt][f];
+                        xc[rt][f] = nv;
+                    }
+                }
+            }
+            {
+                const int pcl = ((INVERSE ? 0 : L - 1) + alt) & 1;      // the last layer transformed slot 2f + 1 - pcl; its result sits in xc
+#pragma unroll
+                for (int rt = 0; rt < R; ++rt)
+#pragma unroll
+                    for (int f = 0; f < NF; ++f) {
+                        xr[rt][2 * f] = pcl ? xc[rt][f] : xt[rt][f];
+                        xr[rt][2 * f + 1] = pcl ? xt[rt][f] : xc[rt][f];
+                    }
+            }
+        } else                                               // STAGED: one loop over the stages, paced by the LDS double buffer
         for (int si = 0; si < nstages; ++si) {
             // stage si has landed (this wave's pieces: vmcnt; every wave's: the barrier), and every wave is done
             // reading the other buffer, which the next stage may now overwrite
@@ -393,15 +533,6 @@ k_flow_bx3(const uint32_t *__restrict__ wp, Geo3 g, int L, int alt, const float 
             const int pc = (l + alt) & 1;
             const int nt = (g.HT - ch * g.TC) < g.TC ? (g.HT - ch * g.TC) : g.TC;
             if (rem == 0) {                                  // layer start: GEMM1's B operand, accumulators
-                if constexpr (!STAGED && CQ > 0) {
-                    // the conditions' bf16 terms are the same in every layer: left alone, the compiler computes them once per row
-                    // group, finds no register for them and parks them in scratch (written through to HBM, re-read per layer);
-                    // 7 VALU operations per value and layer instead
-#pragma unroll
-                    for (int rt = 0; rt < R; ++rt)
-#pragma unroll
-                        for (int u = 0; u < CQ; ++u) asm volatile("" : "+v"(cr[rt][u]));
-                }
                 if (pc) build_bin<NF, CQ, 1, R>(xr, cr, bin); else build_bin<NF, CQ, 0, R>(xr, cr, bin);
 #pragma unroll
                 for (int rt = 0; rt < R; ++rt)
@@ -411,12 +542,8 @@ k_flow_bx3(const uint32_t *__restrict__ wp, Geo3 g, int L, int alt, const float 
                         else out[rt][u] = *reinterpret_cast<const f4 *>(b2base + (size_t)l * g.b2_floats + (u * 4 + q) * 4);
                     }
             }
-            if constexpr (STAGED) {
+            {
                 const uint32_t *sb = lds + (si & 1) * g.SD;
-                if (net == 0) run_stage<NF, CQ, R, 0, ACT, NOUT>(sb, g, lane, nt, bin, out);
-                else run_stage<NF, CQ, R, 1, ACT, NOUT>(sb, g, lane, nt, bin, out);
-            } else {
-                const uint32_t *__restrict__ sb = stage_src(si);
                 if (net == 0) run_stage<NF, CQ, R, 0, ACT, NOUT>(sb, g, lane, nt, bin, out);
                 else run_stage<NF, CQ, R, 1, ACT, NOUT>(sb, g, lane, nt, bin, out);
             }
