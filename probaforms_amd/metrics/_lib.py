@@ -19,6 +19,8 @@ CVM_MAX_N = 1 << 20        # pooled rows pfm_metric1d's Cramer-von Mises sums ho
 KNN_MAX_K = 16             # PFM_KNN_MAX_K: the largest nearest_k of pfm_prdc
 ENERGY_TILE = 64           # PFM_ENERGY_TILE: rows per side of a pair tile of pfm_energy
 ENERGY_REP_BLOCK = 16      # PFM_ENERGY_REP_BLOCK: replicates per count tile of pfm_energy
+PERM_ENERGY, PERM_GAUSS = 0, 1   # PFM_PERM_*: the pair value of pfm_perm_form
+KEY_MASK_ALL = 2 ** 64 - 1 # pfm_perm_labels' key_mask in use: all 64 key bits count
 PFM_EINVAL, PFM_EUNSUPPORTED, PFM_EWORKSPACE = -1, -2, -3
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -43,6 +45,10 @@ _SIGNATURES = {
     "pfm_prdc": (C.c_int, [_VP, _VP, _I64, _VP, _I64, _I64, _VP, _VP, _I64, _I64, _VP, _VP, _VP, _VP, _SZ]),
     "pfm_energy_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64]),
     "pfm_energy": (C.c_int, [_VP, _VP, _I64, _VP, _I64, _I64, _VP, _VP, _I64, _VP, _VP, _SZ]),
+    "pfm_perm_labels_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
+    "pfm_perm_labels": (C.c_int, [_VP, C.c_uint64, C.c_uint64, _I64, _I64, _I64, _I64, _VP, _VP, _SZ]),
+    "pfm_perm_form_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64]),
+    "pfm_perm_form": (C.c_int, [_VP, C.c_int, C.c_double, _VP, _I64, _I64, _I64, _VP, _I64, _VP, _VP, _SZ]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -194,3 +200,38 @@ def energy_status(Xr, Xf, idx_r, idx_f, reps, sums, ws):
 
 def energy(*args):
     check(energy_status(*args), "pfm_energy")
+
+
+def perm_labels_workspace_bytes(reps, n, n_first):
+    return int(lib().pfm_perm_labels_workspace_bytes(int(reps), int(n), int(n_first)))
+
+
+def perm_labels_status(seed, key_mask, first_perm, reps, n, n_first, labels, ws):
+    """enqueue labellings first_perm .. first_perm + reps - 1 of n pooled rows (n_first ones each) on the current stream
+    and return the status; labels is a uint8 view of reps * n elements"""
+    assert labels.numel() == reps * n
+    return int(lib().pfm_perm_labels(torch.cuda.current_stream().cuda_stream, int(seed), int(key_mask), int(first_perm),
+                                     int(reps), int(n), int(n_first), _ptr(labels, torch.uint8, "labels"),
+                                     _ptr(ws, torch.uint8, "workspace"), ws.numel()))
+
+
+def perm_labels(*args):
+    check(perm_labels_status(*args), "pfm_perm_labels")
+
+
+def perm_form_workspace_bytes(n, d, n_first, reps):
+    return int(lib().pfm_perm_form_workspace_bytes(int(n), int(d), int(n_first), int(reps)))
+
+
+def perm_form_status(kind, gamma, Z, n_first, labels, reps, S, ws):
+    """enqueue the signed pair sums of `reps` labellings of the pooled sample Z [n, d] on the current stream and return the
+    status; labels is a uint8 view of reps * n elements, S a float64 view of reps elements"""
+    n, d = Z.shape
+    assert labels.numel() == reps * n and S.numel() == reps
+    return int(lib().pfm_perm_form(torch.cuda.current_stream().cuda_stream, int(kind), float(gamma),
+                                   _ptr(Z, torch.float64, "Z"), n, d, int(n_first), _ptr(labels, torch.uint8, "labels"),
+                                   int(reps), _ptr(S, torch.float64, "S"), _ptr(ws, torch.uint8, "workspace"), ws.numel()))
+
+
+def perm_form(*args):
+    check(perm_form_status(*args), "pfm_perm_form")

@@ -20,6 +20,10 @@
  *   pfm_energy        the energy distance's three pair sums (real x real, fake x fake, real x fake Euclidean
  *                     distances) of every replicate: each distance is formed once per call on the original rows
  *                     and weighted by the replicates' draw counts, one float64 multiply-add per replicate and pair
+ *   pfm_perm_labels   random relabellings of the pooled sample for a permutation test, drawn on the device from a
+ *                     counter-based generator, and
+ *   pfm_perm_form     the signed pair sum of every relabelling (energy or Gaussian kernel): each pair value is formed once
+ *                     per call, one float64 multiply-add per relabelling and pair
  *
  * Conventions (as include/rnvp_hip.h)
  *   - every pointer is a DEVICE pointer; sizes are plain integers;
@@ -194,6 +198,44 @@ size_t pfm_energy_workspace_bytes(int64_t nr, int64_t nf, int64_t d, int64_t rep
 int pfm_energy(void *stream, const double *Xr, int64_t nr, const double *Xf, int64_t nf, int64_t d,
                const int32_t *idx_r, const int32_t *idx_f, int64_t reps, double *sums, void *workspace,
                size_t workspace_bytes);
+
+/* ---- permutation two-sample tests (pf_perm.hip) -------------------------------------------------- */
+
+#define PFM_PERM_ENERGY 0       /* G(a, b) = |z_a - z_b|, formed as pfm_energy forms it */
+#define PFM_PERM_GAUSS  1       /* G(a, b) = exp(-(gamma |z_a - z_b|^2)) of the same squared distance */
+
+/* bytes of workspace pfm_perm_labels needs: nothing is kept there, the figure is the least a caller can allocate (0: the
+   arguments are invalid) */
+size_t pfm_perm_labels_workspace_bytes(int64_t reps, int64_t n, int64_t n_first);
+
+/*
+ * `reps` random labellings of n pooled rows with exactly n_first ones each, labels [reps, n] (every byte written, 0 or 1).
+ * Labelling r of the call has the global index p = first_perm + r, and depends on (seed, key_mask, p, n, n_first) only: it is
+ * the same bytes whatever call or group makes it.  Row a's sort key is
+ *   (w0 | w1 << 32) & key_mask,   (w0, w1, w2, w3) = Philox4x32-10(counter (a, 0, p, 0), key (seed & 0xffffffff, seed >> 32)),
+ * and row a gets label 1 iff its rank in ascending lexicographic order of (key, a) is below n_first.  key_mask is all ones in
+ * use; a narrow mask forces ties (3: n / 4-fold), and 0 orders by index alone: rows 0 .. n_first - 1 get the ones.
+ * 1 <= n_first < n <= 2^31 - 1, 0 <= first_perm, first_perm + reps <= 2^32.
+ */
+int pfm_perm_labels(void *stream, uint64_t seed, uint64_t key_mask, int64_t first_perm, int64_t reps,
+                    int64_t n, int64_t n_first, uint8_t *labels, void *workspace, size_t workspace_bytes);
+
+/* bytes of workspace pfm_perm_form needs: the workgroups' partial sums (0: the arguments are invalid or a size overflows) */
+size_t pfm_perm_form_workspace_bytes(int64_t n, int64_t d, int64_t n_first, int64_t reps);
+
+/*
+ * The signed quadratic form of `reps` labellings of the pooled sample Z [n, d] (the first sample's n_first rows, then the
+ * second's n - n_first): with s[r, a] = +(n - n_first) where labels[r, a] is non-zero and -n_first otherwise (integers, exact
+ * in float64),
+ *   S[r] = sum_a sum_b s[r, a] s[r, b] G(a, b)   over all ordered pairs, the diagonal included,
+ * G as `kind` says (gamma matters for PFM_PERM_GAUSS only and must then be positive and finite).  With the observed labelling
+ * (a < n_first) the caller gets the energy distance's D^2 = -S / (n_first (n - n_first))^2 and the biased
+ * MMD^2 = +S / (n_first (n - n_first))^2 of the samples as given.  The order of summation depends on (n, d) only, so a
+ * labelling's S is bitwise the same alone, in any group, in any call.  Every element of S [reps] is written.
+ * PFM_EUNSUPPORTED for another kind.
+ */
+int pfm_perm_form(void *stream, int kind, double gamma, const double *Z, int64_t n, int64_t d, int64_t n_first,
+                  const uint8_t *labels, int64_t reps, double *S, void *workspace, size_t workspace_bytes);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,164 @@
+"""energy_test, mmd_test: permutation two-sample tests on the GPU (kernels: csrc/pf_perm.hip, pfm_perm_labels and
+pfm_perm_form; host side: _boot.py, _m1d.py).  The reference has no such test; the arguments follow energy_distance.
+
+The question the bootstrap (mean, std) of the other metrics does not answer: can the difference between the real and the
+generated sample be told from chance?  Pool the nr + nf rows, relabel them at random n_permutations times (nr rows "real"
+each time) and see where the statistic of the samples as given falls among the relabelled ones:
+  pvalue = (1 + #{null >= statistic}) / (1 + n_permutations).
+
+With s[a] = +nf on a row labelled real and -nr otherwise, the statistic of a labelling is the signed pair sum
+S = sum_ab s[a] s[b] G(a, b) over the pooled rows, scaled by (nr nf)^2:
+  energy_test   G = |z_a - z_b|,            D^2 = -S / (nr nf)^2: energy_distance_full_sample(squared=True), the V-statistic,
+                which rounding may leave a few 1e-16 below 0;
+  mmd_test      G = exp(-gamma |z_a - z_b|^2), MMD^2 = +S / (nr nf)^2: the reference's mmd_calc, mean K_XX + mean K_YY - 2 mean
+                K_XY with the diagonals included.  gamma = 1 / (2 median^2) of the pooled distance matrix, or 1 / (2 bandwidth^2);
+                the pooled sample does not change under relabelling, so gamma is the same for every labelling.
+G does not depend on the labelling: the kernel forms every pair value once per group of labellings and spends one float64
+multiply-add per labelling and pair.
+
+The labellings are drawn on the device by a counter-based generator (Philox4x32-10; pf_metrics.h states the definition), seeded
+by the ONE draw a call makes from numpy's global generator: lo, hi = np.random.randint(0, 2**32, size=2, dtype=np.uint64),
+seed = lo | hi << 32.  A seeded call is bitwise reproducible.  The observed labelling is not drawn.
+
+Inputs may be numpy arrays, array-likes or torch tensors; a CUDA tensor stays on its device.  NaN or infinite input, a bad
+n_permutations, a non-bool standardize and a bad bandwidth raise ValueError before anything is drawn.  Importing this module
+needs no GPU.
+"""
+import collections
+import math
+
+import numpy as np
+import torch
+
+from . import _boot, _lib, _m1d
+
+TwoSampleTest = collections.namedtuple("TwoSampleTest", ("statistic", "pvalue", "null"))
+
+GROUP_BYTES = 256 << 20     # labels and kernel workspace of one group of labellings
+MAX_GROUP = 1 << 16         # labellings per group, at most
+
+
+def group_size(n_labellings, rows, ws_per_rep):
+    """labellings per group: a group's label bytes [G, rows] and its kernel workspace stay within GROUP_BYTES"""
+    return int(max(1, min(n_labellings, MAX_GROUP, GROUP_BYTES // (rows + max(1, ws_per_rep)))))
+
+
+def _check(X_real, X_fake, n_permutations, standardize, bandwidth=None):
+    if isinstance(n_permutations, bool) or not isinstance(n_permutations, (int, np.integer)) or n_permutations < 1:
+        raise ValueError("n_permutations must be a positive integer, got %r" % (n_permutations,))
+    if not isinstance(standardize, (bool, np.bool_)):
+        raise ValueError("standardize must be a bool, got %r" % (standardize,))
+    if bandwidth is not None:
+        ok = isinstance(bandwidth, (int, float, np.integer, np.floating)) and not isinstance(bandwidth, (bool, np.bool_))
+        if not ok or not (math.isfinite(bandwidth) and bandwidth > 0):
+            raise ValueError("bandwidth must be None or a positive finite number, got %r" % (bandwidth,))
+    _m1d.check_args(X_real, X_fake, 1)
+
+
+def _median(Xr, Xf):
+    """the median of the pooled distance matrix of the samples as given: pfm_mmd's identity replicate"""
+    (nr, d), nf = Xr.shape, Xf.shape[0]
+    ws = torch.empty(_lib.mmd_workspace_bytes(nr, nf, d, 1), dtype=torch.uint8, device=Xr.device)
+    out = torch.empty(2, dtype=torch.float64, device=Xr.device)
+    ir = torch.arange(nr, dtype=torch.int32, device=Xr.device)
+    jf = torch.arange(nf, dtype=torch.int32, device=Xr.device)
+    _lib.mmd(Xr, Xf, ir, jf, 1, out[:1], out[1:], ws)
+    return float(out[0])
+
+
+def pvalue_of(statistic, null):
+    """(1 + #{null >= statistic}) / (1 + n_permutations)"""
+    null = np.asarray(null, np.float64)
+    return np.float64(1 + int(np.count_nonzero(null >= statistic))) / np.float64(1 + null.size)
+
+
+def values_of(S, nr, nf, kind):
+    """[n] raw signed pair sums -> D^2 = -S / (nr nf)^2 (energy) or MMD^2 = +S / (nr nf)^2 (Gauss); a zero sum gives +0.0"""
+    S = np.asarray(S, np.float64)
+    den = np.float64((nr * nf) ** 2)
+    return (0.0 - S) / den if kind == _lib.PERM_ENERGY else (0.0 + S) / den
+
+
+def _test(kind, X_real, X_fake, n_permutations, standardize, bandwidth):
+    _check(X_real, X_fake, n_permutations, standardize, bandwidth)
+    Xr, Xf = _boot.prepare(X_real, X_fake, ("X_real", "X_fake"), 1)
+    (nr, d), nf = Xr.shape, Xf.shape[0]
+    N, total = nr + nf, int(n_permutations) + 1                       # the observed labelling in front of the drawn ones
+    with torch.cuda.device(Xr.device):
+        if standardize:
+            Xr, Xf = _boot.standardize(Xr, Xf)
+        gamma = 0.0
+        if kind == _lib.PERM_GAUSS:
+            sigma = float(bandwidth) if bandwidth is not None else _median(Xr, Xf)
+            if not sigma > 0:
+                raise ValueError("the median pairwise distance is 0, so gamma = 1 / (2 median^2) is infinite (too few "
+                                 "distinct rows)")
+            gamma = 1.0 / (2 * sigma ** 2)
+            if not (math.isfinite(gamma) and gamma > 0):
+                raise ValueError("gamma = 1 / (2 sigma^2) is not a positive finite number for sigma = %r" % (sigma,))
+        lo, hi = np.random.randint(0, 2 ** 32, size=2, dtype=np.uint64)
+        seed = int(lo) | int(hi) << 32
+
+        dev = Xr.device
+        Z = torch.cat([Xr, Xf], dim=0).contiguous()
+        G = group_size(total, N, _lib.perm_form_workspace_bytes(N, d, nr, 1))
+        ws = torch.empty(max(_lib.perm_form_workspace_bytes(N, d, nr, G), _lib.perm_labels_workspace_bytes(G, N, nr)),
+                         dtype=torch.uint8, device=dev)
+        labels = torch.empty((G, N), dtype=torch.uint8, device=dev)
+        S = torch.empty(total, dtype=torch.float64, device=dev)
+        for start in range(0, total, G):
+            reps = min(G, total - start)
+            lab = labels[:reps]
+            own = 1 if start == 0 else 0                              # labelling 0 of the call is the observed one
+            if own:
+                lab[0] = (torch.arange(N, device=dev) < nr).to(torch.uint8)
+            if reps > own:
+                _lib.perm_labels(seed, _lib.KEY_MASK_ALL, start + own - 1, reps - own, N, nr, lab[own:], ws)
+            _lib.perm_form(kind, gamma, Z, nr, lab, reps, S[start:start + reps], ws)
+        V = values_of(S.cpu().numpy(), nr, nf, kind)
+    statistic, null = V[0], V[1:].copy()
+    return TwoSampleTest(statistic, pvalue_of(statistic, null), null)
+
+
+def energy_test(X_real, X_fake, n_permutations=999, standardize=False):
+    '''
+    Permutation test of the energy distance (Szekely & Rizzo) between real and fake samples.
+
+    Parameters:
+    -----------
+    X_real: array of shape [n_samples, n_features] (numpy, array-like or torch; a CUDA tensor stays on the device)
+        Real sample.
+    X_fake: array of shape [m_samples, n_features]
+        Generated sample.
+    n_permutations: int
+        The number of random relabellings of the pooled sample. Default = 999.
+    standardize: boolean
+        If True, the StandardScaler fitted on the real sample is applied to both. Default = False.
+
+    Return:
+    -------
+    TwoSampleTest(statistic, pvalue, null): D^2 of the samples as given (energy_distance_full_sample(squared=True)),
+    (1 + #{null >= statistic}) / (1 + n_permutations), and D^2 of every relabelling [n_permutations]; numpy float64.
+    '''
+    return _test(_lib.PERM_ENERGY, X_real, X_fake, n_permutations, standardize, None)
+
+
+def mmd_test(X_real, X_fake, n_permutations=999, standardize=False, bandwidth=None):
+    '''
+    Permutation test of the Maximum Mean Discrepancy (RBF kernel) between real and fake samples.
+
+    Parameters:
+    -----------
+    X_real, X_fake, n_permutations, standardize: as energy_test.
+    bandwidth: None or float
+        sigma of the kernel exp(-d^2 / (2 sigma^2)). Default = None: the median of the pooled distance matrix of the samples
+        as given, as the reference's mmd_calc takes it.
+
+    Return:
+    -------
+    TwoSampleTest(statistic, pvalue, null): mean K_XX + mean K_YY - 2 mean K_XY of the samples as given (diagonals included),
+    (1 + #{null >= statistic}) / (1 + n_permutations), and the same of every relabelling [n_permutations]; numpy float64.
+
+    Raises ValueError if bandwidth is None and the median pairwise distance is 0.
+    '''
+    return _test(_lib.PERM_GAUSS, X_real, X_fake, n_permutations, standardize, bandwidth)
