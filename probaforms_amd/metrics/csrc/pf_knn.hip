@@ -10,81 +10,26 @@
 //                    in LDS and added to an int32 array with one integer atomic per fake column and tile
 //   k_prdc_final     one workgroup per replicate: P = #{c > 0}, Rc, Dn = sum c, Cv as int64
 // Every distance is the squared Euclidean distance accumulated as fma(df, df, acc) over the features in order, in float64:
-// the d^2 of pf_metrics.hip's tile_d2.  No square root is taken and no norm / dot-product identity is used: a duplicated
-// row's distance is exactly 0 and the comparisons `d^2 < radius^2` are between values of one formula.  The outputs are order
-// statistics (values) and integer counts (integer atomics are exact and order-free), so a call is bitwise reproducible and a
-// replicate's result does not depend on the grid.
+// tile_d2 of pf_pairtile.h, pfm_mmd's chunk_d2.  No square root is taken and no norm / dot-product identity is used: a
+// duplicated row's distance is exactly 0 and the comparisons `d^2 < radius^2` are between values of one formula.  The outputs
+// are order statistics (values) and integer counts (integer atomics are exact and order-free), so a call is bitwise
+// reproducible and a replicate's result does not depend on the grid.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
 #include <stdint.h>
 
 #include "pf_metrics.h"
-
-#define PFM_TRY(x)                                              \
-    do {                                                        \
-        hipError_t e_ = (x);                                    \
-        if (e_ != hipSuccess) return (int)e_;                   \
-    } while (0)
+#include "pf_pairtile.h"
 
 namespace {
 
-constexpr int NT = 256;            // threads per workgroup, every kernel
-constexpr int TILE = 64;           // rows per side of a pair tile: thread (ti, tj) owns rows ti + 16 a, columns tj + 16 b
-constexpr int TPAD = TILE + 1;     // LDS row of one feature of a tile (odd stride: staging writes spread over banks)
-constexpr int DC = 16;             // features staged per chunk
-
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-__host__ __device__ inline int64_t tiles_of(int64_t n) { return (n + TILE - 1) / TILE; }
-
-struct Rows {                       // one replicate's resampled sample X[idx]
+struct Rows {                       // one replicate's resampled sample X[idx]: a row source of pf_pairtile.h
     const double *X;
     const int32_t *idx;
     int64_t n, d;
     __device__ const double *row(int64_t r) const { return X + (int64_t)idx[r] * d; }
 };
-
-// features k0 .. k0 + dc - 1 of rows r0 .. r0 + 63 into sm[feature][row]; rows past the sample's end are zeros
-__device__ inline void stage(const Rows &s, int64_t r0, int64_t k0, int dc, double (*sm)[TPAD]) {
-    for (int e = threadIdx.x; e < TILE * dc; e += NT) {
-        const int row = e / dc, col = e - row * dc;
-        const int64_t g = r0 + row;
-        sm[col][row] = g < s.n ? s.row(g)[k0 + col] : 0.0;
-    }
-}
-
-// d^2 of the 4 x 4 pairs a thread owns: rows I0 + ti + 16 a of A against rows J0 + tj + 16 b of B (tile_d2 of
-// pf_metrics.hip with two samples).  a_resident: A has one feature chunk (d <= DC) and the caller staged it in sA once
-// for the whole sweep.
-__device__ inline void rect_d2(const Rows &A, int64_t I0, const Rows &B, int64_t J0, bool a_resident, double (*sA)[TPAD],
-                               double (*sB)[TPAD], double acc[4][4]) {
-    const int tid = threadIdx.x, ti = tid >> 4, tj = tid & 15;
-#pragma unroll
-    for (int a = 0; a < 4; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = 0.0;
-    for (int64_t k0 = 0; k0 < A.d; k0 += DC) {
-        const int dc = (int)((A.d - k0) < DC ? (A.d - k0) : DC);
-        __syncthreads();                               // the previous chunk's (or tile's) reads are done
-        if (!a_resident) stage(A, I0, k0, dc, sA);
-        stage(B, J0, k0, dc, sB);
-        __syncthreads();
-        for (int k = 0; k < dc; ++k) {
-            double xa[4], yb[4];
-#pragma unroll
-            for (int a = 0; a < 4; ++a) xa[a] = sA[k][ti + 16 * a];
-#pragma unroll
-            for (int b = 0; b < 4; ++b) yb[b] = sB[k][tj + 16 * b];
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    const double df = xa[a] - yb[b];
-                    acc[a][b] = fma(df, df, acc[a][b]);
-                }
-        }
-    }
-}
 
 // v into the ascending list b of the L smallest values seen (the caller has tested v < b[L - 1]): it replaces the largest
 // and sinks through an unrolled compare-exchange chain; every index is a compile-time constant, so b stays in registers
@@ -117,7 +62,7 @@ __global__ void __launch_bounds__(NT) k_knn_radius(const double *Xr, int64_t nr,
                                                    double *rad_f) {
     __shared__ double sA[DC][TPAD], sB[DC][TPAD];
     __shared__ double heads[2][4][16][16];
-    const int64_t rep = blockIdx.y, ntr = tiles_of(nr);
+    const int64_t rep = blockIdx.y, ntr = tiles_per_side(nr);
     const bool fake = (int64_t)blockIdx.x >= ntr;
     const int64_t bi = fake ? (int64_t)blockIdx.x - ntr : (int64_t)blockIdx.x;
     Rows S;
@@ -136,11 +81,11 @@ __global__ void __launch_bounds__(NT) k_knn_radius(const double *Xr, int64_t nr,
         for (int i = 0; i < L; ++i) best[a][i] = INFINITY;
     }
     const bool resident = d <= DC;
-    if (resident) stage(S, bi * TILE, 0, (int)d, sA);     // (rect_d2 begins with a barrier)
-    const int64_t nb = tiles_of(S.n);
+    if (resident) stage(S, bi * TILE, 0, (int)d, sA);     // (tile_d2 begins with a barrier)
+    const int64_t nb = tiles_per_side(S.n);
     for (int64_t bj = 0; bj < nb; ++bj) {
         double acc[4][4];
-        rect_d2(S, bi * TILE, S, bj * TILE, resident, sA, sB, acc);
+        tile_d2(S, bi * TILE, S, bj * TILE, resident, sA, sB, acc);
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
             const bool in = bj * TILE + tj + 16 * b < S.n;
@@ -218,11 +163,11 @@ __global__ void __launch_bounds__(NT) k_prdc_sweep(const double *Xr, int64_t nr,
     }
     if (tid < TILE) { colcnt[tid] = 0; rowflag[0][tid] = 0; rowflag[1][tid] = 0; }
     const bool resident = d <= DC;
-    if (resident) stage(R, bi * TILE, 0, (int)d, sA);     // (rect_d2 begins with a barrier, which also orders the zero stores)
-    const int64_t nb = tiles_of(nf);
+    if (resident) stage(R, bi * TILE, 0, (int)d, sA);     // (tile_d2 begins with a barrier, which also orders the zero stores)
+    const int64_t nb = tiles_per_side(nf);
     for (int64_t bj = 0; bj < nb; ++bj) {
         double acc[4][4];
-        rect_d2(R, bi * TILE, F, bj * TILE, resident, sA, sB, acc);
+        tile_d2(R, bi * TILE, F, bj * TILE, resident, sA, sB, acc);
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
             const int64_t gj = bj * TILE + tj + 16 * b;
@@ -304,7 +249,7 @@ bool prdc_args_ok(int64_t nr, int64_t nf, int64_t d, int64_t reps, int64_t k) {
 extern "C" size_t pfm_prdc_workspace_bytes(int64_t nr, int64_t nf, int64_t d, int64_t reps, int64_t k) {
     if (!prdc_args_ok(nr, nf, d, reps, k) || k > PFM_KNN_MAX_K) return 0;
     return align256(sizeof(int32_t) * (size_t)reps * (size_t)nf) +
-           align256(sizeof(int32_t) * 2 * (size_t)reps * (size_t)tiles_of(nr));
+           align256(sizeof(int32_t) * 2 * (size_t)reps * (size_t)tiles_per_side(nr));
 }
 
 extern "C" int pfm_prdc(void *stream, const double *Xr, int64_t nr, const double *Xf, int64_t nf, int64_t d,
@@ -316,7 +261,7 @@ extern "C" int pfm_prdc(void *stream, const double *Xr, int64_t nr, const double
     const size_t need = pfm_prdc_workspace_bytes(nr, nf, d, reps, k);
     if (!workspace || workspace_bytes < need) return PFM_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    const int64_t ntr = tiles_of(nr), ntf = tiles_of(nf);
+    const int64_t ntr = tiles_per_side(nr), ntf = tiles_per_side(nf);
     const size_t cbytes = sizeof(int32_t) * (size_t)reps * (size_t)nf;
     int32_t *c = (int32_t *)workspace;
     int32_t *wg = (int32_t *)((char *)workspace + align256(cbytes));

@@ -8,14 +8,14 @@
 // MMD, per replicate, over the pooled rows Z = [X[idx_x]; Y[idx_y]] (m rows), in 2 + 2 * MMD_PASSES launches:
 //   k_mmd_init     state and histograms zeroed; ranks (m*m - 1) / 2 and m*m / 2 of np.median
 //   k_mmd_hist     (per digit) sweeps the upper-triangle 64 x 64 tiles of Z: d^2 of every pair i < j from
-//                  row tiles staged in LDS, features looped in chunks of MMD_DC.  The f64 bit pattern of
+//                  chunk_d2 of pf_pairtile.h, over the gathered rows (tile_d2_pooled).  The f64 bit pattern of
 //                  d^2 >= 0 orders like a uint64: each pair whose key matches the prefix found so far adds
 //                  2 (it is (i, j) and (j, i)) to the LDS histogram of the key's next digit; workgroups
 //                  flush their histograms with integer atomics (exact, order-free)
 //   k_mmd_scan     (per digit) one workgroup per replicate: adds the m diagonal zeros to bucket 0, finds
 //                  the bucket holding each of the two middle ranks, extends the prefixes, zeroes the
 //                  histograms; after the last digit the prefixes ARE the two order statistics
-//   k_mmd_rbf      the same tile sweep and the same d^2, summing exp(-gamma d^2) into XX / YY / XY
+//   k_mmd_rbf      the same tile sweep and the same tile_d2_pooled, summing exp(-gamma d^2) into XX / YY / XY
 //   k_mmd_final    per replicate: the workgroups' partials in order, the three means, mmd
 // Two prefixes are tracked because the two middle ranks may part at any digit; while they agree one
 // histogram serves both.
@@ -30,19 +30,10 @@
 #include <stdint.h>
 
 #include "pf_metrics.h"
-
-#define PFM_TRY(x)                                              \
-    do {                                                        \
-        hipError_t e_ = (x);                                    \
-        if (e_ != hipSuccess) return (int)e_;                   \
-    } while (0)
+#include "pf_pairtile.h"
 
 namespace {
 
-constexpr int NT = 256;            // threads per workgroup, every kernel
-constexpr int TILE = 64;           // rows per side of an MMD pair tile
-constexpr int TPAD = TILE + 1;     // LDS row of one feature of a tile (odd stride: staging writes spread over banks)
-constexpr int MMD_DC = 16;         // features staged per chunk
 constexpr int MMD_PASSES = 6;      // radix digits of the 64-bit key, most significant first
 constexpr int k_shift[MMD_PASSES] = {52, 41, 30, 19, 8, 0};
 constexpr int k_width[MMD_PASSES] = {12, 11, 11, 11, 11, 8};
@@ -61,13 +52,8 @@ struct MmdState {
     int32_t pad[3];
 };
 
-__host__ __device__ inline int64_t tiles_of(int64_t m) {
-    int64_t nb = (m + TILE - 1) / TILE;
-    return nb * (nb + 1) / 2;
-}
-
 inline int64_t mmd_wg_per_rep(int64_t m, int64_t reps) {
-    int64_t T = tiles_of(m);
+    int64_t T = triangle_tiles(m);
     int64_t w = (MMD_TARGET_WG + reps - 1) / reps;
     if (w > T) w = T;
     int64_t wmin = (T + MMD_MAX_TILES_PER_WG - 1) / MMD_MAX_TILES_PER_WG;
@@ -80,60 +66,37 @@ inline int64_t parts_of(int64_t n) {
     return p < 1 ? 1 : (p > MAX_PARTS ? MAX_PARTS : p);
 }
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-struct Pooled {                      // one replicate's pooled sample Z = [X[ix]; Y[iy]]
+struct Pooled {                      // one replicate's pooled sample Z = [X[ix]; Y[iy]]: a row source of pf_pairtile.h
     const double *X, *Y;
     const int32_t *ix, *iy;
-    int64_t nx, m, d;
+    int64_t nx, n, d;
     __device__ const double *row(int64_t r) const {
         return r < nx ? X + (int64_t)ix[r] * d : Y + (int64_t)iy[r - nx] * d;
     }
 };
 
-// linear upper-triangle tile t -> block pair (bi <= bj)
-__device__ inline void tile_decode(int64_t t, int64_t &bi, int64_t &bj) {
-    int64_t r = (int64_t)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-    while (r * (r + 1) / 2 > t) --r;
-    while ((r + 1) * (r + 2) / 2 <= t) ++r;
-    bj = r;
-    bi = t - r * (r + 1) / 2;
-}
-
-// d^2 of the 4 x 4 pairs a thread owns in tile (bi, bj); rows ti + 16 a, columns tj + 16 b.  The ONE place
-// d^2 is computed: the select passes and the RBF pass see identical values.
-__device__ inline void tile_d2(const Pooled &z, int64_t bi, int64_t bj, double (*sA)[TPAD], double (*sB)[TPAD],
-                               double acc[4][4]) {
-    const int tid = threadIdx.x, ti = tid >> 4, tj = tid & 15;
+// tile_d2 of pf_pairtile.h for tile (bi, bj) of one pooled sample, with the two sides staged in ONE loop (both gathers of an
+// element are in flight together).  As two stage() calls k_mmd_hist and k_mmd_rbf measured 6 % slower at 20 000 pooled rows,
+// d = 16 (profiles/r19_pairtile_time.txt), so the MMD kernels keep this loop; the arithmetic is chunk_d2's, the same as everywhere.
+__device__ inline void tile_d2_pooled(const Pooled &z, int64_t bi, int64_t bj, double (*sA)[TPAD], double (*sB)[TPAD],
+                                      double acc[4][4]) {
+    const int tid = threadIdx.x;
 #pragma unroll
     for (int a = 0; a < 4; ++a)
 #pragma unroll
         for (int b = 0; b < 4; ++b) acc[a][b] = 0.0;
     const int64_t I0 = bi * TILE, J0 = bj * TILE;
-    for (int64_t k0 = 0; k0 < z.d; k0 += MMD_DC) {
-        const int dc = (int)((z.d - k0) < MMD_DC ? (z.d - k0) : MMD_DC);
+    for (int64_t k0 = 0; k0 < z.d; k0 += DC) {
+        const int dc = (int)((z.d - k0) < DC ? (z.d - k0) : DC);
         __syncthreads();                               // the previous chunk's reads are done
         for (int e = tid; e < TILE * dc; e += NT) {
             const int row = e / dc, col = e - row * dc;
             const int64_t gi = I0 + row, gj = J0 + row;
-            sA[col][row] = gi < z.m ? z.row(gi)[k0 + col] : 0.0;
-            sB[col][row] = gj < z.m ? z.row(gj)[k0 + col] : 0.0;
+            sA[col][row] = gi < z.n ? z.row(gi)[k0 + col] : 0.0;
+            sB[col][row] = gj < z.n ? z.row(gj)[k0 + col] : 0.0;
         }
         __syncthreads();
-        for (int k = 0; k < dc; ++k) {
-            double xa[4], yb[4];
-#pragma unroll
-            for (int a = 0; a < 4; ++a) xa[a] = sA[k][ti + 16 * a];
-#pragma unroll
-            for (int b = 0; b < 4; ++b) yb[b] = sB[k][tj + 16 * b];
-#pragma unroll
-            for (int a = 0; a < 4; ++a)
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    const double df = xa[a] - yb[b];
-                    acc[a][b] = fma(df, df, acc[a][b]);
-                }
-        }
+        chunk_d2(sA, sB, dc, acc);
     }
 }
 
@@ -141,7 +104,7 @@ __device__ inline Pooled pooled(const double *X, int64_t nx, const double *Y, in
                                 const int32_t *idx_x, const int32_t *idx_y, int64_t rep) {
     Pooled z;
     z.X = X; z.Y = Y; z.ix = idx_x + rep * nx; z.iy = idx_y + rep * ny;
-    z.nx = nx; z.m = nx + ny; z.d = d;
+    z.nx = nx; z.n = nx + ny; z.d = d;
     return z;
 }
 
@@ -164,7 +127,7 @@ __global__ void __launch_bounds__(NT) k_mmd_hist(const double *X, int64_t nx, co
                                                  const int32_t *idx_x, const int32_t *idx_y, const MmdState *st,
                                                  unsigned long long *hist, int shift, int width) {
     __shared__ uint32_t hA[MAX_BINS], hB[MAX_BINS];
-    __shared__ double sA[MMD_DC][TPAD], sB[MMD_DC][TPAD];
+    __shared__ double sA[DC][TPAD], sB[DC][TPAD];
     const int64_t rep = blockIdx.y;
     const Pooled z = pooled(X, nx, Y, ny, d, idx_x, idx_y, rep);
     const int nbins = 1 << width, tid = threadIdx.x, ti = tid >> 4, tj = tid & 15;
@@ -173,19 +136,19 @@ __global__ void __launch_bounds__(NT) k_mmd_hist(const double *X, int64_t nx, co
     const uint64_t pA = st[rep].pref[0], pB = st[rep].pref[1];
     const bool same = st[rep].same != 0;
     for (int b = tid; b < nbins; b += NT) { hA[b] = 0u; hB[b] = 0u; }
-    // (tile_d2 begins with a barrier, which also orders these zero stores before the first count)
-    const int64_t T = tiles_of(z.m);
+    // (tile_d2_pooled begins with a barrier, which also orders these zero stores before the first count)
+    const int64_t T = triangle_tiles(z.n);
     for (int64_t t = blockIdx.x; t < T; t += gridDim.x) {
         int64_t bi, bj;
         tile_decode(t, bi, bj);
         double acc[4][4];
-        tile_d2(z, bi, bj, sA, sB, acc);
+        tile_d2_pooled(z, bi, bj, sA, sB, acc);
 #pragma unroll
         for (int a = 0; a < 4; ++a)
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
                 const int64_t gi = bi * TILE + ti + 16 * a, gj = bj * TILE + tj + 16 * b;
-                if (gi < z.m && gj < z.m && gi < gj) {
+                if (gi < z.n && gj < z.n && gi < gj) {
                     const uint64_t key = (uint64_t)__double_as_longlong(acc[a][b]);
                     const uint32_t dig = (uint32_t)((key >> shift) & bmask);
                     if ((key & hi_mask) == pA) atomicAdd(&hA[dig], 2u);
@@ -260,7 +223,7 @@ __global__ void __launch_bounds__(NT) k_mmd_scan(MmdState *st, unsigned long lon
 __global__ void __launch_bounds__(NT) k_mmd_rbf(const double *X, int64_t nx, const double *Y, int64_t ny, int64_t d,
                                                 const int32_t *idx_x, const int32_t *idx_y, const MmdState *st,
                                                 double *partials) {
-    __shared__ double sA[MMD_DC][TPAD], sB[MMD_DC][TPAD];
+    __shared__ double sA[DC][TPAD], sB[DC][TPAD];
     __shared__ double red[3][NT];
     const int64_t rep = blockIdx.y;
     const Pooled z = pooled(X, nx, Y, ny, d, idx_x, idx_y, rep);
@@ -268,18 +231,18 @@ __global__ void __launch_bounds__(NT) k_mmd_rbf(const double *X, int64_t nx, con
     const double gamma = st[rep].gamma;
     const bool skip = !(st[rep].median > 0.0);              // median 0: the caller raises, no point in the sweep
     double sxx = 0.0, syy = 0.0, sxy = 0.0;
-    const int64_t T = skip ? 0 : tiles_of(z.m);
+    const int64_t T = skip ? 0 : triangle_tiles(z.n);
     for (int64_t t = blockIdx.x; t < T; t += gridDim.x) {
         int64_t bi, bj;
         tile_decode(t, bi, bj);
         double acc[4][4];
-        tile_d2(z, bi, bj, sA, sB, acc);
+        tile_d2_pooled(z, bi, bj, sA, sB, acc);
 #pragma unroll
         for (int a = 0; a < 4; ++a)
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
                 const int64_t gi = bi * TILE + ti + 16 * a, gj = bj * TILE + tj + 16 * b;
-                if (gi < z.m && gj < z.m && gi < gj) {
+                if (gi < z.n && gj < z.n && gi < gj) {
                     const double k = exp(acc[a][b] * -gamma);   // rbf_kernel: K *= -gamma; np.exp(K)
                     if (gi >= nx) syy += k;                     // gi < gj: both in Y
                     else if (gj < nx) sxx += k;

@@ -3,24 +3,11 @@
 #ifndef PF_SCAN1D_H
 #define PF_SCAN1D_H
 
-#include <hip/hip_runtime.h>
-
-#include <stddef.h>
-#include <stdint.h>
-
-#define PFM_TRY(x)                                              \
-    do {                                                        \
-        hipError_t e_ = (x);                                    \
-        if (e_ != hipSuccess) return (int)e_;                   \
-    } while (0)
+#include "pf_common.h"
 
 namespace {
 
-constexpr int NT = 256;          // threads per workgroup, every kernel
 constexpr int IPT = 4;           // tie groups per thread per chunk of the scan
-
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 
 __global__ void __launch_bounds__(NT) k_counts(const int32_t *idx_r, const int32_t *idx_f, int64_t nr, int64_t nf,
                                                int32_t *cnt) {

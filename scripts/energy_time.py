@@ -16,7 +16,7 @@ yardstick for time, tests/test_energy_gpu.py holds (a) against a float64 scipy r
     python scripts/energy_time.py [out.txt] [--reps N] [--yard-reps N] [--shape NxD] [--only-energy]
 
 Under `rocprofv3 --kernel-trace --stats -- python scripts/energy_time.py --only-energy --reps 1 --shape 10000x16` the kernels'
-own times at one shape: k_counts, k_energy_tiles and k_energy_finish (the call then runs twice: warm-up and one).
+own times at one shape: k_counts, k_energy_tiles and k_quad_finish<3> (the call then runs twice: warm-up and one).
 """
 import argparse
 import os

@@ -14,7 +14,7 @@ for time, tests/test_twosample_gpu.py holds (a) against a float64 scipy restatem
     python scripts/twosample_time.py [out.txt] [--reps N] [--yard-reps N] [--shape NxD] [--only-tests]
 
 Under `rocprofv3 --kernel-trace --stats -- python scripts/twosample_time.py --only-tests --reps 1 --shape 10000x16` the kernels' own
-times at one shape: k_perm_labels, k_perm_tiles and k_perm_finish of both tests, and pfm_mmd's median kernels (each test then
+times at one shape: k_perm_labels, k_perm_tiles and k_quad_finish<1> of both tests, and pfm_mmd's median kernels (each test then
 runs three times: warm-up, timed, and once more for the printed result).
 """
 import argparse

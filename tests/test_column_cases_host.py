@@ -24,7 +24,8 @@ def test_constants_are_the_kernels():
     def text(name):
         return open(os.path.join(ROOT, "probaforms_amd", "metrics", "csrc", name)).read()
     scan, m1d, wass = text("pf_scan1d.h"), text("pf_metrics1d.hip"), text("pf_wasserstein.hip")
-    assert "constexpr int NT = 256;" in scan and "constexpr int IPT = 4;" in scan and cc.CHUNK == 256 * 4 and cc.PASS == 256
+    assert '#include "pf_common.h"' in scan and "constexpr int NT = 256;" in text("pf_common.h")
+    assert "constexpr int IPT = 4;" in scan and cc.CHUNK == 256 * 4 and cc.PASS == 256
     assert "constexpr int GP = %d;" % cc.GP in m1d and "constexpr int HIST_LDS = %d;" % cc.HIST_LDS in m1d
     assert "CVM_MAX_N = int64_t(1) << 20;" in m1d and cc.CVM_MAX_N == 1 << 20 == _lib.CVM_MAX_N
     assert "constexpr int WP_LDS = %d;" % cc.WP_LDS in wass and "TILE = WP_LDS / 2" in wass and cc.TILE == cc.WP_LDS // 2

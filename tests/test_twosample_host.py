@@ -218,7 +218,7 @@ def test_header_constants_and_declarations_equal_the_binding():
     assert re.search(r"#define PFM_PERM_GAUSS\s+%d\s" % _lib.PERM_GAUSS, raw)
     assert (_lib.PERM_ENERGY, _lib.PERM_GAUSS) == (tn.ENERGY, tn.GAUSS) and _lib.KEY_MASK_ALL == tn.ALL == 2 ** 64 - 1
     assert tn.TILE == _lib.ENERGY_TILE
-    src = open(os.path.join(ROOT, "probaforms_amd", "metrics", "csrc", "pf_perm.hip")).read()
+    src = open(os.path.join(ROOT, "probaforms_amd", "metrics", "csrc", "pf_quadform.h")).read()
     assert re.search(r"MIN_LIST = %d;" % tn.MIN_LIST, src) and re.search(r"TARGET_WGS = %d;" % tn.TARGET_WGS, src)
     assert "pf_perm.o" in open(os.path.join(ROOT, "probaforms_amd", "metrics", "csrc", "Makefile")).read()
 

@@ -17,7 +17,7 @@ from wasserstein_numpy import standardize  # noqa: F401
 
 ENERGY, GAUSS = 0, 1              # pf_metrics.h PFM_PERM_*
 ALL = 2 ** 64 - 1                 # key_mask in use
-TILE = 64                         # pf_perm.hip: rows per side of a pair tile,
+TILE = 64                         # pf_quadform.h: rows per side of a pair tile,
 MIN_LIST, TARGET_WGS = 4, 2048    # tiles per workgroup at least, workgroups per call about
 M32 = np.uint64(0xFFFFFFFF)
 
