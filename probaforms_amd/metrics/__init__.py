@@ -23,6 +23,7 @@ wrong (fidelity against diversity) where the distances only say how much, and th
     from probaforms_amd.metrics.wasserstein import wasserstein_1d, sliced_wasserstein_distance
     from probaforms_amd.metrics.prdc import prdc, prdc_full_sample     # bootstrapped (mean, std) pairs; the samples as given
     from probaforms_amd.metrics.energy import energy_distance, energy_distance_full_sample
+    from probaforms_amd.metrics.twosample import energy_test, mmd_test, knn_test, nn_accuracy_full_sample   # permutation p-values
 
 `__all__` and the `probaforms.metrics` alias (`probaforms_amd.install_as_probaforms()`) name only the two
 multivariate metrics, so `from probaforms.metrics import kolmogorov_smirnov_1d` raises ImportError there.

@@ -17,6 +17,8 @@ MOMENTS_MAX_D = 4096       # PFM_MOMENTS_MAX_D
 M1D_KS, M1D_CVM, M1D_AD, M1D_AUC, M1D_HIST, M1D_KDE = range(6)
 CVM_MAX_N = 1 << 20        # pooled rows pfm_metric1d's Cramer-von Mises sums hold exactly
 KNN_MAX_K = 16             # PFM_KNN_MAX_K: the largest nearest_k of pfm_prdc
+NN_MAX_K = 16              # PFM_NN_MAX_K: the largest k of pfm_nn_index
+NN_STAGE_MAX_N = 262144    # PFM_NN_STAGE_MAX_N: rows up to which pfm_nn_count keeps a labelling in LDS
 ENERGY_TILE = 64           # PFM_ENERGY_TILE: rows per side of a pair tile of pfm_energy
 ENERGY_REP_BLOCK = 16      # PFM_ENERGY_REP_BLOCK: replicates per count tile of pfm_energy
 PERM_ENERGY, PERM_GAUSS = 0, 1   # PFM_PERM_*: the pair value of pfm_perm_form
@@ -49,6 +51,10 @@ _SIGNATURES = {
     "pfm_perm_labels": (C.c_int, [_VP, C.c_uint64, C.c_uint64, _I64, _I64, _I64, _I64, _VP, _VP, _SZ]),
     "pfm_perm_form_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64]),
     "pfm_perm_form": (C.c_int, [_VP, C.c_int, C.c_double, _VP, _I64, _I64, _I64, _VP, _I64, _VP, _VP, _SZ]),
+    "pfm_nn_index_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
+    "pfm_nn_index": (C.c_int, [_VP, _VP, _I64, _I64, _I64, _VP, _VP, _VP, _SZ]),
+    "pfm_nn_count_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
+    "pfm_nn_count": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _I64, _VP, _VP, _SZ]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -235,3 +241,40 @@ def perm_form_status(kind, gamma, Z, n_first, labels, reps, S, ws):
 
 def perm_form(*args):
     check(perm_form_status(*args), "pfm_perm_form")
+
+
+def nn_index_workspace_bytes(n, d, k):
+    return int(lib().pfm_nn_index_workspace_bytes(int(n), int(d), int(k)))
+
+
+def nn_index_status(Z, k, nbr, d2, ws):
+    """enqueue the k nearest other rows of every row of Z [n, d] on the current stream and return the status; nbr is an int32
+    view of n * k elements (the rows, nearest first, ties by row index), d2 a float64 view of as many (their squared
+    distances)"""
+    n, d = Z.shape
+    assert nbr.numel() == n * k == d2.numel()
+    return int(lib().pfm_nn_index(torch.cuda.current_stream().cuda_stream, _ptr(Z, torch.float64, "Z"), n, d, int(k),
+                                  _ptr(nbr, torch.int32, "nbr"), _ptr(d2, torch.float64, "d2"),
+                                  _ptr(ws, torch.uint8, "workspace"), ws.numel()))
+
+
+def nn_index(*args):
+    check(nn_index_status(*args), "pfm_nn_index")
+
+
+def nn_count_workspace_bytes(n, k, reps):
+    return int(lib().pfm_nn_count_workspace_bytes(int(n), int(k), int(reps)))
+
+
+def nn_count_status(nbr, n, k, labels, reps, counts, ws):
+    """enqueue the same-label neighbour counts of `reps` labellings on the current stream and return the status; nbr is an
+    int32 view of n * k elements, labels a uint8 view of reps * n, counts an int64 view of reps * 2 elements (slots with both
+    labels non-zero, slots with both zero)"""
+    assert nbr.numel() == n * k and labels.numel() == reps * n and counts.numel() == reps * 2
+    return int(lib().pfm_nn_count(torch.cuda.current_stream().cuda_stream, _ptr(nbr, torch.int32, "nbr"), int(n), int(k),
+                                  _ptr(labels, torch.uint8, "labels"), int(reps), _ptr(counts, torch.int64, "counts"),
+                                  _ptr(ws, torch.uint8, "workspace"), ws.numel()))
+
+
+def nn_count(*args):
+    check(nn_count_status(*args), "pfm_nn_count")

@@ -24,6 +24,10 @@
  *                     counter-based generator, and
  *   pfm_perm_form     the signed pair sum of every relabelling (energy or Gaussian kernel): each pair value is formed once
  *                     per call, one float64 multiply-add per relabelling and pair
+ *   pfm_nn_index      every pooled row's k nearest other rows, which rows they are and their squared distances, ordered by
+ *                     (distance, row index), and
+ *   pfm_nn_count      per labelling, how many (row, neighbour) slots carry the same label on both sides: the
+ *                     nearest-neighbour two-sample test, whose neighbour table does not depend on the labelling
  *
  * Conventions (as include/rnvp_hip.h)
  *   - every pointer is a DEVICE pointer; sizes are plain integers;
@@ -54,7 +58,7 @@ extern "C" {
 #define PFM_EINVAL       (-1)   /* NULL pointer, non-positive size, index range       */
 #define PFM_EUNSUPPORTED (-2)   /* d too large for the moments kernels' LDS row tile;
                                    a Wasserstein order p other than 1 or 2;
-                                   nearest_k above PFM_KNN_MAX_K                         */
+                                   nearest_k above PFM_KNN_MAX_K; k above PFM_NN_MAX_K    */
 #define PFM_EWORKSPACE   (-3)   /* workspace smaller than *_workspace_bytes() says      */
 
 #define PFM_VERSION 101         /* pfm_version(): bumped whenever an argument list changes */
@@ -236,6 +240,43 @@ size_t pfm_perm_form_workspace_bytes(int64_t n, int64_t d, int64_t n_first, int6
  */
 int pfm_perm_form(void *stream, int kind, double gamma, const double *Z, int64_t n, int64_t d, int64_t n_first,
                   const uint8_t *labels, int64_t reps, double *S, void *workspace, size_t workspace_bytes);
+
+/* ---- nearest-neighbour two-sample test (pf_nn.hip) ------------------------------------------------ */
+
+#define PFM_NN_MAX_K 16         /* k of pfm_nn_index: the per-thread lists of (d^2, row) live in registers */
+#define PFM_NN_STAGE_MAX_N 262144   /* rows up to which pfm_nn_count keeps a labelling in LDS, one bit per row (32 KB);
+                                       above it the label bytes are read from global memory */
+
+/* bytes of workspace pfm_nn_index needs: nothing is kept there, the figure is the least a caller can allocate (0: the
+   arguments are invalid, k above PFM_NN_MAX_K included, or a size overflows) */
+size_t pfm_nn_index_workspace_bytes(int64_t n, int64_t d, int64_t k);
+
+/*
+ * The k nearest OTHER rows of every row of Z [n, d]: nbr[a, r] is the row of rank r < k in ascending order of
+ * (d^2, row index), so among equal squared distances the smaller row index comes first, and d2[a, r] its squared distance, the
+ * D2 of pfm_prdc: fma(df, df, acc) over the features in order, no square root, no norm / dot-product identity, bitwise what
+ * the other entry points form for the pair.  Row a is left out by its index, not by its distance: a duplicate of row a is a
+ * neighbour at distance exactly 0.  nbr [n, k] int32, d2 [n, k]; every element is written.
+ * PFM_EINVAL for n < 2, d < 1, k < 1, k > n - 1 or n > 2^31 - 1, PFM_EUNSUPPORTED for k > PFM_NN_MAX_K; on any error nothing is
+ * written.
+ */
+int pfm_nn_index(void *stream, const double *Z, int64_t n, int64_t d, int64_t k, int32_t *nbr, double *d2,
+                 void *workspace, size_t workspace_bytes);
+
+/* bytes of workspace pfm_nn_count needs: the counts of the slices a labelling's slots are cut into (0: the arguments are
+   invalid or a size overflows) */
+size_t pfm_nn_count_workspace_bytes(int64_t n, int64_t k, int64_t reps);
+
+/*
+ * For each of `reps` labellings of the n rows (labels [reps, n], as pfm_perm_labels writes them), over the n k slots (a, r)
+ * of a neighbour table nbr [n, k] (entries in [0, n): the caller's duty):
+ *   counts[p, 0] = #{(a, r) : labels[p, a] != 0 and labels[p, nbr[a, r]] != 0}
+ *   counts[p, 1] = #{(a, r) : labels[p, a] == 0 and labels[p, nbr[a, r]] == 0}
+ * Integer work in a fixed order: a labelling's counts are the same alone, in any group, in any call.  counts [reps, 2] int64,
+ * every element written.  n, k, reps >= 1, n <= 2^31 - 1, reps <= 2^31 - 1.
+ */
+int pfm_nn_count(void *stream, const int32_t *nbr, int64_t n, int64_t k, const uint8_t *labels, int64_t reps,
+                 int64_t *counts, void *workspace, size_t workspace_bytes);
 
 #ifdef __cplusplus
 }

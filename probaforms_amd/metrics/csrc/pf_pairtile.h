@@ -4,7 +4,7 @@
 // thread (ti, tj) = (tid >> 4, tid & 15) owns the 4 x 4 pairs of rows ti + 16 a and columns tj + 16 b.  The two row sets are
 // staged through LDS in chunks of DC features, and d^2 is accumulated as fma(df, df, acc) over the features in order, in
 // float64 (chunk_d2).  No square root is taken and no norm / dot-product identity is used.  Every kernel that needs a
-// distance gets it from chunk_d2: pf_knn.hip, pf_energy.hip and pf_perm.hip through tile_d2, pf_metrics.hip through its
+// distance gets it from chunk_d2: pf_knn.hip, pf_nn.hip, pf_energy.hip and pf_perm.hip through tile_d2, pf_metrics.hip through its
 // tile_d2_pooled, which differs in how it stages only.  So across kernels a duplicated row is at distance exactly 0,
 // `d^2 < radius^2` compares values of one formula, and a statistic recomputed by another entry point has the same bits.
 #ifndef PF_PAIRTILE_H

@@ -1,5 +1,6 @@
-"""energy_test, mmd_test: permutation two-sample tests on the GPU (kernels: csrc/pf_perm.hip, pfm_perm_labels and
-pfm_perm_form; host side: _boot.py, _m1d.py).  The reference has no such test; the arguments follow energy_distance.
+"""energy_test, mmd_test, knn_test: permutation two-sample tests on the GPU (kernels: csrc/pf_perm.hip, pfm_perm_labels and
+pfm_perm_form; csrc/pf_nn.hip, pfm_nn_index and pfm_nn_count; host side: _boot.py, _m1d.py).  The reference has no such test;
+the arguments follow energy_distance.
 
 The question the bootstrap (mean, std) of the other metrics does not answer: can the difference between the real and the
 generated sample be told from chance?  Pool the nr + nf rows, relabel them at random n_permutations times (nr rows "real"
@@ -16,13 +17,18 @@ S = sum_ab s[a] s[b] G(a, b) over the pooled rows, scaled by (nr nf)^2:
 G does not depend on the labelling: the kernel forms every pair value once per group of labellings and spends one float64
 multiply-add per labelling and pair.
 
+knn_test (Schilling 1986; Henze 1988) has a statistic that reads as a rate: the share of the rows' nearest_k nearest neighbours
+in the pooled sample that carry the row's own label; with nearest_k = 1 the leave-one-out 1-NN classifier accuracy.  The
+neighbours do not depend on the labelling either: one sweep over the pairs finds them (pfm_nn_index), and a labelling then
+costs N nearest_k label look-ups (pfm_nn_count).  It draws and uses the same labellings as energy_test.
+
 The labellings are drawn on the device by a counter-based generator (Philox4x32-10; pf_metrics.h states the definition), seeded
 by the ONE draw a call makes from numpy's global generator: lo, hi = np.random.randint(0, 2**32, size=2, dtype=np.uint64),
 seed = lo | hi << 32.  A seeded call is bitwise reproducible.  The observed labelling is not drawn.
 
 Inputs may be numpy arrays, array-likes or torch tensors; a CUDA tensor stays on its device.  NaN or infinite input, a bad
-n_permutations, a non-bool standardize and a bad bandwidth raise ValueError before anything is drawn.  Importing this module
-needs no GPU.
+n_permutations, a non-bool standardize, a bad bandwidth and a bad nearest_k raise ValueError before anything is drawn.
+Importing this module needs no GPU.
 """
 import collections
 import math
@@ -33,6 +39,8 @@ import torch
 from . import _boot, _lib, _m1d
 
 TwoSampleTest = collections.namedtuple("TwoSampleTest", ("statistic", "pvalue", "null"))
+KnnTest = collections.namedtuple("KnnTest", ("statistic", "pvalue", "null", "real", "fake"))
+NnAccuracy = collections.namedtuple("NnAccuracy", ("total", "real", "fake"))
 
 GROUP_BYTES = 256 << 20     # labels and kernel workspace of one group of labellings
 MAX_GROUP = 1 << 16         # labellings per group, at most
@@ -162,3 +170,99 @@ def mmd_test(X_real, X_fake, n_permutations=999, standardize=False, bandwidth=No
     Raises ValueError if bandwidth is None and the median pairwise distance is 0.
     '''
     return _test(_lib.PERM_GAUSS, X_real, X_fake, n_permutations, standardize, bandwidth)
+
+
+def _check_k(nearest_k, N):
+    ok = isinstance(nearest_k, (int, np.integer)) and not isinstance(nearest_k, (bool, np.bool_))
+    if not ok or not 1 <= nearest_k <= min(_lib.NN_MAX_K, N - 1):
+        raise ValueError("nearest_k must be an integer in 1 .. min(%d, n_real + n_fake - 1 = %d), got %r"
+                         % (_lib.NN_MAX_K, N - 1, nearest_k))
+
+
+def shares_of(counts, nr, nf, k):
+    """[n, 2] int64 counts (both labelled real, both labelled fake) -> float64 [n, 3] same-label shares of all rows' neighbours,
+    of the real rows' and of the fake rows': Python ints divided, rounded once"""
+    return np.array([[(int(cr) + int(cf)) / ((nr + nf) * k), int(cr) / (nr * k), int(cf) / (nf * k)] for cr, cf in counts],
+                    dtype=np.float64).reshape(-1, 3)
+
+
+def _knn(X_real, X_fake, n_permutations, nearest_k, standardize):
+    """-> (shares_of the observed labelling [3], the statistic of the drawn ones [n_permutations]); n_permutations = None draws
+    nothing"""
+    _check(X_real, X_fake, 1 if n_permutations is None else n_permutations, standardize)
+    _check_k(nearest_k, _boot._check_2d(X_real, "X_real")[1][0] + _boot._check_2d(X_fake, "X_fake")[1][0])
+    Xr, Xf = _boot.prepare(X_real, X_fake, ("X_real", "X_fake"), 1)
+    (nr, d), nf = Xr.shape, Xf.shape[0]
+    N, k = nr + nf, int(nearest_k)
+    total = 1 + int(n_permutations or 0)                              # the observed labelling in front of the drawn ones
+    with torch.cuda.device(Xr.device):
+        if standardize:
+            Xr, Xf = _boot.standardize(Xr, Xf)
+        if total > 1:
+            lo, hi = np.random.randint(0, 2 ** 32, size=2, dtype=np.uint64)
+            seed = int(lo) | int(hi) << 32
+
+        dev = Xr.device
+        Z = torch.cat([Xr, Xf], dim=0).contiguous()
+        nbr = torch.empty((N, k), dtype=torch.int32, device=dev)
+        d2 = torch.empty((N, k), dtype=torch.float64, device=dev)
+        _lib.nn_index(Z, k, nbr, d2, torch.empty(_lib.nn_index_workspace_bytes(N, d, k), dtype=torch.uint8, device=dev))
+        G = group_size(total, N, _lib.nn_count_workspace_bytes(N, k, 1))
+        ws = torch.empty(max(_lib.nn_count_workspace_bytes(N, k, G), _lib.perm_labels_workspace_bytes(G, N, nr)),
+                         dtype=torch.uint8, device=dev)
+        labels = torch.empty((G, N), dtype=torch.uint8, device=dev)
+        counts = torch.empty((total, 2), dtype=torch.int64, device=dev)
+        for start in range(0, total, G):
+            reps = min(G, total - start)
+            lab = labels[:reps]
+            own = 1 if start == 0 else 0                              # labelling 0 of the call is the observed one
+            if own:
+                lab[0] = (torch.arange(N, device=dev) < nr).to(torch.uint8)
+            if reps > own:
+                _lib.perm_labels(seed, _lib.KEY_MASK_ALL, start + own - 1, reps - own, N, nr, lab[own:], ws)
+            _lib.nn_count(nbr, N, k, lab, reps, counts[start:start + reps], ws)
+        C = counts.cpu().tolist()                                     # Python ints: every ratio is rounded once
+    return shares_of(C[:1], nr, nf, k)[0], np.array([(cr + cf) / (N * k) for cr, cf in C[1:]], dtype=np.float64)
+
+
+def knn_test(X_real, X_fake, n_permutations=999, nearest_k=1, standardize=False):
+    '''
+    Nearest-neighbour permutation two-sample test (Schilling 1986; Henze 1988) between real and fake samples. With
+    nearest_k = 1 the statistic is the leave-one-out 1-NN classifier accuracy (Lopez-Paz & Oquab 2017).
+
+    Parameters:
+    -----------
+    X_real, X_fake, n_permutations, standardize: as energy_test; the same labellings are drawn from the same seed draw.
+    nearest_k: int
+        The number of nearest neighbours of a row, in 1 .. min(16, n_samples + m_samples - 1). Default = 1. The neighbours are
+        the nearest other rows of the pooled sample by squared Euclidean distance, ties by row index (real rows first); a
+        duplicate of a row is its neighbour at distance 0.
+
+    Return:
+    -------
+    KnnTest(statistic, pvalue, null, real, fake): the share of all N * nearest_k neighbour slots whose neighbour carries the
+    row's own label; (1 + #{null >= statistic}) / (1 + n_permutations); the share under every relabelling [n_permutations];
+    the same share among the real rows' and among the fake rows' slots; numpy float64.
+
+    Under the null hypothesis the expected statistic is (nr (nr - 1) + nf (nf - 1)) / (N (N - 1)), about 0.5 for samples of
+    equal size; samples that differ push it towards 1. pvalue is the upper tail. A statistic BELOW the null values is what
+    generated rows that copy real rows look like (each row's nearest neighbour is its copy in the other sample; 0.0 for an exact
+    copy at nearest_k = 1): null is returned so that the lower tail, (1 + #{null <= statistic}) / (1 + n_permutations), can be
+    taken by hand.
+    '''
+    if n_permutations is None:
+        raise ValueError("n_permutations must be a positive integer, got None")
+    (statistic, real, fake), null = _knn(X_real, X_fake, n_permutations, nearest_k, standardize)
+    return KnnTest(statistic, pvalue_of(statistic, null), null, real, fake)
+
+
+def nn_accuracy_full_sample(X_real, X_fake, nearest_k=1, standardize=False):
+    '''
+    The statistic of knn_test alone: nothing is drawn and numpy's global generator is left untouched.
+
+    Return:
+    -------
+    NnAccuracy(total, real, fake): knn_test's statistic, real and fake; with nearest_k = 1 the leave-one-out 1-NN accuracy over
+    all rows, over the real rows and over the fake rows; numpy float64.
+    '''
+    return NnAccuracy(*_knn(X_real, X_fake, None, nearest_k, standardize)[0])
