@@ -13,6 +13,8 @@
 // __builtin_amdgcn_sched_barrier(0) between the blocks pins that order; inside a block the MFMAs
 // issue first and the VALU work runs in their shadow.
 #pragma once
+#include <type_traits>
+
 #include "rnvp_mfma.h"
 
 namespace rnvp {
@@ -50,6 +52,23 @@ constexpr bool kUseX4 = false;
 #else
 constexpr bool kUseX4 = true;
 #endif
+
+// The net-split training kernel of d <= 16 (k_mfma_train<2, ., ., 1, ...>), developer switches for A/B timing
+// (profiles/r08_train_seams_ab.txt): RNVP_NS_SADDR=0 keeps the per-lane 64-bit fragment addresses in its tile loops,
+// RNVP_NS_OWNACC=0 the forward seam that carries both nets' accumulators and selects by role per lane, RNVP_NS_LDSBASE=0 the
+// backward tile body's transposed reads from pointers with folded constants.
+// Same-box A/B of rnvp_loss_grad at 65 536 rows of C2: 0.2674 ms -> 0.2561 with the scalar bases, 0.2487 with the LDS bases too,
+// 0.2470 with all three; results bit for bit the same.
+#ifndef RNVP_NS_SADDR
+#define RNVP_NS_SADDR 1
+#endif
+#ifndef RNVP_NS_OWNACC
+#define RNVP_NS_OWNACC 1
+#endif
+#ifndef RNVP_NS_LDSBASE
+#define RNVP_NS_LDSBASE 1
+#endif
+constexpr bool kNsSaddr = RNVP_NS_SADDR != 0, kNsOwnAcc = RNVP_NS_OWNACC != 0, kNsLdsBase = RNVP_NS_LDSBASE != 0;
 
 // tanh(v) = 1 - 2 / (1 + e^{2v}) with u = 2*log2(e)*v arriving PRE-SCALED: k_pack_weights folds
 // kTanhScale into the packed W1 and b1, so GEMM1's accumulator already is u.  Per value: one
@@ -92,6 +111,24 @@ typedef const __attribute__((address_space(1))) f4 *gf4_ptr;      // keeps the l
 __device__ __forceinline__ gf4_ptr opaque(const float *p) {
     asm volatile("" : "+v"(p));
     return (gf4_ptr)p;
+}
+
+// A weight fragment as wave-uniform base (an SGPR pair) + the lane's 32-bit float offset + an immediate: the load needs no
+// address arithmetic on the VALU (the idiom of rnvp_bx3.hip's direct form).  The base is opaque like opaque()'s pointer, so the
+// load stays where it is written.
+typedef const __attribute__((address_space(1))) float *gw_ptr;
+__device__ __forceinline__ gw_ptr sbase_w(const float *p) {
+    asm volatile("" : "+s"(p));
+    return (gw_ptr)p;
+}
+__device__ __forceinline__ f4 gl_w4(gw_ptr base, unsigned off) { return *reinterpret_cast<const __attribute__((address_space(1))) f4 *>(base + off); }
+// an LDS position as an opaque 32-bit address: what is added to it later stays an immediate of the DS instruction instead of
+// being folded with the constants already inside the pointer (which pushes paired reads past their 8-bit offset fields)
+typedef __attribute__((address_space(3))) float *lds_ptr;
+__device__ __forceinline__ lds_ptr lds_base(float *p) {
+    lds_ptr l = (lds_ptr)p;
+    asm volatile("" : "+v"(l));
+    return l;
 }
 
 // Row I/O of lane group q: features q*2NF .. q*2NF + 2NF - 1 and conditions q*CQ .. q*CQ + CQ - 1.
@@ -422,10 +459,13 @@ __device__ __forceinline__ void run_tiles(const float *__restrict__ W, const Geo
 // GEMM1 accumulator register, as before) by 4 outputs (A, pre-packed per lane) for rows 4rg..4rg+3.
 // Partial sums over the lane groups q are combined once per layer by a two-step reduce-scatter.
 // Measured on MI355X: 8 x 4x4x1 take 37 ns against 58 ns for the 4 x 16x16x4 they replace.
-template <int CQ, int R, int PC, int NET, int ACT, bool BX = false>
+// NO == 2 (net-split training kernel): the caller keeps the accumulators of the wave's own net only, outx[R][2], and NET = 0
+// addresses them whichever net `tile0` selects.  SB (same caller): tile0 is wave-uniform and the fragment loads of the tile
+// loop take scalar bases (sbase_w) -- no VALU address arithmetic in the loop.
+template <int CQ, int R, int PC, int NET, int ACT, bool BX = false, int NO = 4, bool SB = false>
 __device__ __forceinline__ void run_tiles_x4(const float *__restrict__ W, const Geo &g, int lane, int tile0,
                                              int ntiles, const float (&xr)[R][4],
-                                             const float (&cr)[R][CQ > 0 ? CQ : 1], f4 (&outx)[R][4],
+                                             const float (&cr)[R][CQ > 0 ? CQ : 1], f4 (&outx)[R][NO],
                                              const f4 (*bin)[SplitDims<2, CQ>::NI1] = nullptr,
                                              const TilePre<2, CQ> *pre = nullptr) {
     constexpr int NF = 2;
@@ -434,13 +474,31 @@ __device__ __forceinline__ void run_tiles_x4(const float *__restrict__ W, const 
     const float *pA1 = W + (BX ? g.oA1S : g.oA1) + ((size_t)tile0 * K4 * 64 + lane) * 4;
     const float *pB1 = W + g.oB1 + ((size_t)tile0 * 4 + q) * 4;
     const float *pA2 = W + g.oA2X + ((size_t)tile0 * 2 * 64 + lane) * 4;
+    // SB: the sections' wave-uniform starts at tile0; a lane adds its own offset in the load
+    const float *uA1 = W + (BX ? g.oA1S : g.oA1) + (size_t)tile0 * K4 * 256, *uB1 = W + g.oB1 + (size_t)tile0 * 16;
+    const float *uA2 = W + g.oA2X + (size_t)tile0 * 2 * 256;
+    const unsigned lo4 = lane * 4, qo4 = q * 4;
     const int last = ntiles - 1;
     struct St { f4 a1n[K4], b1n, a2c[2], acc[R]; };        // two alternating pipeline states: see run_tiles
     St s0, s1;
     {
         f4 a1c[K4], b1c;
         bool have = false;
-        if constexpr (!BX) {
+        if constexpr (SB) {
+            have = true;
+            const int t1 = last < 1 ? last : 1;
+            const gw_ptr g1 = sbase_w(uA1), gb = sbase_w(uB1), g2 = sbase_w(uA2);
+            const gw_ptr g1n = sbase_w(uA1 + (size_t)t1 * K4 * 256), gbn = sbase_w(uB1 + t1 * 16);
+#pragma unroll
+            for (int k4 = 0; k4 < K4; ++k4) a1c[k4] = gl_w4(g1, lo4 + k4 * 256);
+            b1c = gl_w4(gb, qo4);
+#pragma unroll
+            for (int o = 0; o < 2; ++o) s0.a2c[o] = gl_w4(g2, lo4 + o * 256);
+#pragma unroll
+            for (int k4 = 0; k4 < K4; ++k4) s0.a1n[k4] = gl_w4(g1n, lo4 + k4 * 256);
+            s0.b1n = gl_w4(gbn, qo4);
+        }
+        if constexpr (!BX && !SB) {
             if (pre) {          // loaded ahead by the caller (TilePre)
                 have = true;
 #pragma unroll
@@ -474,11 +532,21 @@ __device__ __forceinline__ void run_tiles_x4(const float *__restrict__ W, const 
     };
     auto step = [&](const St &c, St &nx, int t) {
         const int t2 = (t + 2 < last) ? t + 2 : last;
+        if constexpr (SB) {
+            const gw_ptr g1 = sbase_w(uA1 + (size_t)t2 * K4 * 256), gb = sbase_w(uB1 + t2 * 16);
+            const gw_ptr g2 = sbase_w(uA2 + (size_t)(t + 1) * 2 * 256);
+#pragma unroll
+            for (int k4 = 0; k4 < K4; ++k4) nx.a1n[k4] = gl_w4(g1, lo4 + k4 * 256);
+            nx.b1n = gl_w4(gb, qo4);
+#pragma unroll
+            for (int o = 0; o < 2; ++o) nx.a2c[o] = gl_w4(g2, lo4 + o * 256);
+        } else {
 #pragma unroll
         for (int k4 = 0; k4 < K4; ++k4) nx.a1n[k4] = *opaque(pA1 + ((size_t)t2 * K4 + k4) * 256);
         nx.b1n = *opaque(pB1 + t2 * 16);
 #pragma unroll
         for (int o = 0; o < 2; ++o) nx.a2c[o] = *opaque(pA2 + ((size_t)(t + 1) * 2 + o) * 256);
+        }
         __builtin_amdgcn_sched_barrier(0);
         f4 hv[R];
         constexpr int RB = (R % 2 == 0) ? 2 : 1;
@@ -609,7 +677,26 @@ __device__ __forceinline__ void layer_forward_ns(const float *__restrict__ W, co
     f4 bin[BX ? R : 1][SplitDims<NF, CQ>::NI1];
     if constexpr (BX) build_bin<NF, CQ, PC, R>(xr, cr, bin);
     float own[R][NF];
-    if constexpr (NF == 2 && kUseX4) {
+    if constexpr (NF == 2 && kUseX4 && kNsOwnAcc) {
+        // the wave keeps the accumulators of its own net only, and `role` (wave-uniform: the caller hands it over in an SGPR)
+        // picks the net's tiles and its half of the bias by address: one copy of the tile loop serves both nets
+        const float *b2 = W + g.oB2 + q * 4 + 2 * role;
+        const float bias0 = b2[0], bias1 = b2[1];
+        f4 outx[R][2];
+#pragma unroll
+        for (int rt = 0; rt < R; ++rt)
+#pragma unroll
+            for (int u = 0; u < 2; ++u) outx[rt][u] = f4{0.f, 0.f, 0.f, 0.f};
+        run_tiles_x4<CQ, R, PC, 0, ACT, BX, 2, kNsSaddr>(W, g, lane, role * g.HT, g.HT, xr, cr, outx, bin);
+#pragma unroll
+        for (int rt = 0; rt < R; ++rt) {
+            float s4[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) s4[i] = swap_add32(outx[rt][0][i], outx[rt][1][i]);
+            own[rt][0] = swap_add16(s4[0], s4[2]) + bias0;
+            own[rt][1] = swap_add16(s4[1], s4[3]) + bias1;
+        }
+    } else if constexpr (NF == 2 && kUseX4) {
         const f4 bias2 = *reinterpret_cast<const f4 *>(W + g.oB2 + q * 4);
         f4 outx[R][4];
 #pragma unroll
@@ -617,7 +704,7 @@ __device__ __forceinline__ void layer_forward_ns(const float *__restrict__ W, co
 #pragma unroll
             for (int u = 0; u < 4; ++u) outx[rt][u] = f4{0.f, 0.f, 0.f, 0.f};
         if (role == 0) {
-            run_tiles_x4<CQ, R, PC, 0, ACT, BX>(W, g, lane, 0, g.HT, xr, cr, outx, bin);
+            run_tiles_x4<CQ, R, PC, 0, ACT, BX, 4, kNsSaddr>(W, g, lane, 0, g.HT, xr, cr, outx, bin);
 #pragma unroll
             for (int rt = 0; rt < R; ++rt) {
                 float s4[4];
@@ -627,7 +714,7 @@ __device__ __forceinline__ void layer_forward_ns(const float *__restrict__ W, co
                 own[rt][1] = swap_add16(s4[1], s4[3]) + bias2[1];
             }
         } else {
-            run_tiles_x4<CQ, R, PC, 1, ACT, BX>(W, g, lane, g.HT, g.HT, xr, cr, outx, bin);
+            run_tiles_x4<CQ, R, PC, 1, ACT, BX, 4, kNsSaddr>(W, g, lane, g.HT, g.HT, xr, cr, outx, bin);
 #pragma unroll
             for (int rt = 0; rt < R; ++rt) {
                 float s4[4];
@@ -664,6 +751,32 @@ __device__ __forceinline__ void layer_forward_ns(const float *__restrict__ W, co
 #pragma unroll
         for (int f = 0; f < NF; ++f) xown[(rt * NF + f) * 64 + lane] = own[rt][f];
     __syncthreads();
+    if constexpr (NF == 2 && kUseX4 && kNsOwnAcc) {
+        // MODE 2 only (the training kernel).  One scalar branch on the wave's role instead of two per-lane selects per value
+        static_assert(MODE == 2, "the net-split layer serves the training kernel");
+        float oth[R][NF];
+#pragma unroll
+        for (int rt = 0; rt < R; ++rt)
+#pragma unroll
+            for (int f = 0; f < NF; ++f) oth[rt][f] = xother[(rt * NF + f) * 64 + lane];
+        auto couple = [&](const float (&tva)[R][NF], const float (&sva)[R][NF], float *rec, auto is_t) {
+#pragma unroll
+            for (int rt = 0; rt < R; ++rt)
+#pragma unroll
+                for (int f = 0; f < NF; ++f) {
+                    const float tv = tva[rt][f], sv = sva[rt][f];
+                    const int e = 2 * f + 1 - PC;
+                    const float es = expf(sv), xv = xr[rt][e];
+                    rec[((rt * 2 * NF) + f) * 64] = decltype(is_t)::value ? xv : es;
+                    xr[rt][e] = fmaf(xv, es, tv);
+                    ld[rt] += sv;
+                }
+        };
+        // the pair shares one scratch record: the t wave saves the layer input, the s wave exp(s)
+        if (role == 0) couple(own, oth, scr + lane, std::true_type{});
+        else couple(oth, own, scr + NF * 64 + lane, std::false_type{});
+        return;
+    }
 #pragma unroll
     for (int rt = 0; rt < R; ++rt) {
 #pragma unroll

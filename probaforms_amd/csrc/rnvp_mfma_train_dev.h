@@ -224,7 +224,10 @@ __device__ __forceinline__ void layer_bwd(const float *__restrict__ W, const Geo
     constexpr int KS1 = D::KS1, K4 = D::K4, OTL = D::OTL, NT2 = D::NT2, KP4 = D::KP4, NTI = D::NTI,
                   MTI = D::MTI, KSP = D::KSP, SIN = D::SIN;
     const int q = lane >> 4, r = lane & 15, tid = wave * 64 + lane;
-    const int role = NS ? (wave >> 2) : 0;
+    // SB (d <= 16, net split): the wave's net in an SGPR and the tile loop's weight fragments as scalar base + the lane's 32-bit
+    // offset + an immediate (sbase_w / gl_w4, rnvp_mfma_layer.h): no VALU address arithmetic in the tile body
+    constexpr bool SB = NF == 2 && NS == 1 && kNsSaddr;
+    const int role = NS ? (SB ? __builtin_amdgcn_readfirstlane(wave >> 2) : (wave >> 2)) : 0;
     const int HT = g.HT;
     const int ht_lo = TS ? tile_lo : 0, ht_hi = TS ? tile_hi : HT;
     constexpr bool W2C = D::template w2c<NS>();
@@ -314,14 +317,42 @@ __device__ __forceinline__ void layer_bwd(const float *__restrict__ W, const Geo
     //    (rnvp_mfma_layer.h): every phase runs over all R row tiles so that dependent MFMA chains
     //    interleave, LDS round trips are covered by the input-gradient MFMAs, and the weight
     //    fragments of the next tile are in flight for a whole iteration.
+    // LB (d <= 16, net split): the lane's read positions in the transposition tiles and in the g_out^T image as opaque 32-bit LDS
+    // addresses, one per tile / per row-tile half, made once per layer: in the tile body every transposed read is base + an offset
+    // below 1 KiB, which the DS offset fields hold -- no v_add_u32 of a folded constant per paired read
+    constexpr bool LB = NF == 2 && NS == 1 && W2C && kNsLdsBase && !(kAblate & 1);
+    constexpr int RHL = (R >= 4) ? 2 : R;
+    lds_ptr hrd[2 * RHL], grd[R / RHL];
+    if constexpr (LB) {
+#pragma unroll
+        for (int t = 0; t < 2 * RHL; ++t) hrd[t] = lds_base(bufH + t * 16 * kTS + q * kTS + r);
+#pragma unroll
+        for (int h = 0; h < R / RHL; ++h) grd[h] = lds_base(bufG + (h * RHL * 16 + q) * GS + 2 * (r & 3));
+    }
     auto net_pass = [&](auto net_c) {
         constexpr int net = decltype(net_c)::value;
         const float *pA1 = W + g.oA1 + ((size_t)net * HT * K4 * 64 + lane) * 4;
         const float *pB1 = W + g.oB1 + ((size_t)net * HT * 4 + q) * 4;
         const float *pA2T = W + g.oA2T + ((size_t)net * HT * OTL * 64 + lane) * 4;
         const float *pA1T = W + (X4 ? g.oA1X : g.oA1T) + ((size_t)net * HT * NGI * 64 + lane) * 4;
+        // SB: the sections' wave-uniform starts for this net; a lane adds lo4 / qo4 in the load
+        const float *uA1 = W + g.oA1 + (size_t)net * HT * K4 * 256, *uB1 = W + g.oB1 + (size_t)net * HT * 16;
+        const float *uA2T = W + g.oA2T + (size_t)net * HT * OTL * 256, *uA1T = W + (X4 ? g.oA1X : g.oA1T) + (size_t)net * HT * NGI * 256;
+        const unsigned lo4 = lane * 4, qo4 = q * 4;
         f4 a1[K4], a2t[OTL], a1t[NGI], b1;
         bool have = false;
+        if constexpr (SB) {
+            have = true;
+            const gw_ptr s1 = sbase_w(uA1 + (size_t)ht_lo * K4 * 256), sb = sbase_w(uB1 + ht_lo * 16);
+            const gw_ptr s2 = sbase_w(uA2T + (size_t)ht_lo * OTL * 256), s3 = sbase_w(uA1T + (size_t)ht_lo * NGI * 256);
+#pragma unroll
+            for (int k4 = 0; k4 < K4; ++k4) a1[k4] = gl_w4(s1, lo4 + k4 * 256);
+            b1 = gl_w4(sb, qo4);
+#pragma unroll
+            for (int o = 0; o < OTL; ++o) a2t[o] = gl_w4(s2, lo4 + o * 256);
+#pragma unroll
+            for (int m = 0; m < NGI; ++m) a1t[m] = gl_w4(s3, lo4 + m * 256);
+        }
         if constexpr (TS) {
             if (use_pre) {          // loaded ahead (BwdPre)
                 have = true;
@@ -353,7 +384,17 @@ __device__ __forceinline__ void layer_bwd(const float *__restrict__ W, const Geo
             // (profiles/r06_bwd_inplace_ab.txt)
             constexpr bool INPL = NF >= 4;
             f4 na1[K4], na2t[OTL], na1t[NGI], nb1;
-            if constexpr (!INPL) {
+            if constexpr (SB) {
+                const gw_ptr s1 = sbase_w(uA1 + (size_t)nx * K4 * 256), sb = sbase_w(uB1 + nx * 16);
+                const gw_ptr s2 = sbase_w(uA2T + (size_t)nx * OTL * 256), s3 = sbase_w(uA1T + (size_t)nx * NGI * 256);
+#pragma unroll
+                for (int k4 = 0; k4 < K4; ++k4) na1[k4] = gl_w4(s1, lo4 + k4 * 256);
+                nb1 = gl_w4(sb, qo4);
+#pragma unroll
+                for (int o = 0; o < OTL; ++o) na2t[o] = gl_w4(s2, lo4 + o * 256);
+#pragma unroll
+                for (int m = 0; m < NGI; ++m) na1t[m] = gl_w4(s3, lo4 + m * 256);
+            } else if constexpr (!INPL) {
 #pragma unroll
                 for (int k4 = 0; k4 < K4; ++k4) na1[k4] = *opaque(pA1 + ((size_t)nx * K4 + k4) * 256);
                 nb1 = *opaque(pB1 + nx * 16);
@@ -438,6 +479,13 @@ __device__ __forceinline__ void layer_bwd(const float *__restrict__ W, const Geo
                     for (int u = 0; u < RH; ++u)
 #pragma unroll
                         for (int ks = 0; ks < 4; ++ks) {
+                            if constexpr (LB) {      // every offset fits the DS offset fields of a paired read
+                                hT[u][ks] = hrd[2 * u][4 * ks * kTS];
+                                pT[u][ks] = hrd[2 * u + 1][4 * ks * kTS];
+                                const f2 gv = *reinterpret_cast<const __attribute__((address_space(3))) f2 *>(grd[r0 / RH] + (u * 16 + 4 * ks) * GS);
+                                gB[u][ks].x = gv[0]; gB[u][ks].y = gv[1];
+                                continue;
+                            }
                             if (!(kAblate & 1)) {
                                 hT[u][ks] = bufH[(2 * u) * 16 * kTS + (4 * ks + q) * kTS + r];
                                 pT[u][ks] = bufH[(2 * u + 1) * 16 * kTS + (4 * ks + q) * kTS + r];
@@ -780,7 +828,9 @@ __device__ __forceinline__ void train_body(const float *__restrict__ wp, const G
     constexpr int XW = R * NF * 64;                       // floats one wave exchanges per layer (NS)
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int pw = wave & (WV - 1), role = NS ? wave >> 2 : 0;     // row owner index; net of this wave (NS)
+    // row owner index; net of this wave (NS) -- for d <= 16 in an SGPR: the role picks a net's tiles by scalar address
+    constexpr bool SROLE = NS == 1 && NF == 2 && (kNsSaddr || kNsOwnAcc);
+    const int pw = wave & (WV - 1), role = NS ? (SROLE ? __builtin_amdgcn_readfirstlane(wave >> 2) : wave >> 2) : 0;
     const int q = lane >> 4, r = lane & 15;
     constexpr int SLOTN = DM::template slot<NS>(), TBN = DM::template tbn<R, NS>();
     float *tb = lds + NW * SLOTN + wave * TBN;
