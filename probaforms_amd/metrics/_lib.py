@@ -47,6 +47,9 @@ _SIGNATURES = {
     "pfm_prdc": (C.c_int, [_VP, _VP, _I64, _VP, _I64, _I64, _VP, _VP, _I64, _I64, _VP, _VP, _VP, _VP, _SZ]),
     "pfm_energy_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64]),
     "pfm_energy": (C.c_int, [_VP, _VP, _I64, _VP, _I64, _I64, _VP, _VP, _I64, _VP, _VP, _SZ]),
+    "pfm_sinkhorn_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64]),
+    "pfm_sinkhorn": (C.c_int, [_VP, _VP, _I64, _VP, _I64, _I64, _VP, _VP, _I64, C.c_int, C.c_double, _I64, _VP, _VP, _VP,
+                               _VP, _SZ]),
     "pfm_perm_labels_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
     "pfm_perm_labels": (C.c_int, [_VP, C.c_uint64, C.c_uint64, _I64, _I64, _I64, _I64, _VP, _VP, _SZ]),
     "pfm_perm_form_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64]),
@@ -206,6 +209,30 @@ def energy_status(Xr, Xf, idx_r, idx_f, reps, sums, ws):
 
 def energy(*args):
     check(energy_status(*args), "pfm_energy")
+
+
+def sinkhorn_workspace_bytes(nr, nf, d, reps):
+    return int(lib().pfm_sinkhorn_workspace_bytes(int(nr), int(nf), int(d), int(reps)))
+
+
+def sinkhorn_status(Xr, Xf, idx_r, idx_f, reps, p, eps, n_sinkhorn, value, drift, potentials, ws):
+    """enqueue `reps` replicates of the debiased Sinkhorn divergence (n_sinkhorn + 1 steps) on the current stream and return
+    the status; value / drift are float64 views of reps elements, potentials None or a float64 view of reps * 2 * (nr + nf)
+    elements ((f, g) then (u, v) on the pooled rows)"""
+    nr, d = Xr.shape
+    nf = Xf.shape[0]
+    assert Xf.shape[1] == d and idx_r.numel() == reps * nr and idx_f.numel() == reps * nf
+    assert value.numel() == reps == drift.numel() and (potentials is None or potentials.numel() == reps * 2 * (nr + nf))
+    return int(lib().pfm_sinkhorn(torch.cuda.current_stream().cuda_stream, _ptr(Xr, torch.float64, "X_real"), nr,
+                                  _ptr(Xf, torch.float64, "X_fake"), nf, d, _ptr(idx_r, torch.int32, "idx_real"),
+                                  _ptr(idx_f, torch.int32, "idx_fake"), int(reps), int(p), float(eps), int(n_sinkhorn),
+                                  _ptr(value, torch.float64, "value"), _ptr(drift, torch.float64, "drift"),
+                                  _ptr(potentials, torch.float64, "potentials", nullable=True),
+                                  _ptr(ws, torch.uint8, "workspace"), ws.numel()))
+
+
+def sinkhorn(*args):
+    check(sinkhorn_status(*args), "pfm_sinkhorn")
 
 
 def perm_labels_workspace_bytes(reps, n, n_first):

@@ -20,6 +20,9 @@
  *   pfm_energy        the energy distance's three pair sums (real x real, fake x fake, real x fake Euclidean
  *                     distances) of every replicate: each distance is formed once per call on the original rows
  *                     and weighted by the replicates' draw counts, one float64 multiply-add per replicate and pair
+ *   pfm_sinkhorn      the debiased Sinkhorn divergence (entropic optimal transport, cost |x - y|^p) of every replicate: the
+ *                     costs are re-formed tile by tile on the original rows in every iteration, the replicates' draw counts
+ *                     are the marginal weights, one float64 exp per replicate, pair and iteration
  *   pfm_perm_labels   random relabellings of the pooled sample for a permutation test, drawn on the device from a
  *                     counter-based generator, and
  *   pfm_perm_form     the signed pair sum of every relabelling (energy or Gaussian kernel): each pair value is formed once
@@ -57,7 +60,7 @@ extern "C" {
 #define PFM_OK            0
 #define PFM_EINVAL       (-1)   /* NULL pointer, non-positive size, index range       */
 #define PFM_EUNSUPPORTED (-2)   /* d too large for the moments kernels' LDS row tile;
-                                   a Wasserstein order p other than 1 or 2;
+                                   a Wasserstein order or Sinkhorn cost power p other than 1 or 2;
                                    nearest_k above PFM_KNN_MAX_K; k above PFM_NN_MAX_K    */
 #define PFM_EWORKSPACE   (-3)   /* workspace smaller than *_workspace_bytes() says      */
 
@@ -202,6 +205,37 @@ size_t pfm_energy_workspace_bytes(int64_t nr, int64_t nf, int64_t d, int64_t rep
 int pfm_energy(void *stream, const double *Xr, int64_t nr, const double *Xf, int64_t nf, int64_t d,
                const int32_t *idx_r, const int32_t *idx_f, int64_t reps, double *sums, void *workspace,
                size_t workspace_bytes);
+
+/* ---- Sinkhorn divergence (pf_sinkhorn.hip) --------------------------------------------------------- */
+
+/* bytes of workspace pfm_sinkhorn needs: the draw counts, their logarithms and three buffers of potentials, 60 bytes per
+   replicate and pooled row; nothing of the size of the pair matrix (0: the arguments are invalid or a size overflows) */
+size_t pfm_sinkhorn_workspace_bytes(int64_t nr, int64_t nf, int64_t d, int64_t reps);
+
+/*
+ * `reps` replicates of the debiased Sinkhorn divergence (Genevay et al. 2018; Feydy et al. 2019) between the resampled sets,
+ * taken as the ORIGINAL rows with weights a = count_r / nr, b = count_f / nf.  Cost C(x, y) = |x - y|^p, p = 1 or 2, from the
+ * squared distance of pfm_energy (fma(df, df, acc) over the features in order; one sqrt for p = 1: a duplicated row costs
+ * exactly 0).  With
+ *   softmin(h, C, w)[i] = -eps log sum_j w_j exp((h_j - C_ij) / eps)      over the columns of non-zero weight, evaluated with
+ * the row's running maximum subtracted, four potentials start at 0: f (on R, against F), g (on F, against R), u (on R, against
+ * R), v (on F, against F).  Each of n_sinkhorn iterations replaces all four from the previous iteration's values,
+ *   f <- (f + softmin(g, C_RF, b)) / 2     g <- (g + softmin(f, C_FR, a)) / 2
+ *   u <- (u + softmin(u, C_RR, a)) / 2     v <- (v + softmin(v, C_FF, b)) / 2
+ * and one last step takes the same four softmins without the averaging, again from the old values.  Then
+ *   value[r] = sum_i a_i (f_i - u_i) + sum_j b_j (g_j - v_j)            over the rows of non-zero count
+ *   drift[r] = the largest |change| of a potential of such a row in the last averaged step (0 for n_sinkhorn = 0)
+ *   potentials[r, 0] = (f, g), potentials[r, 1] = (u, v) after the last step, on the pooled rows (real rows first), the finite
+ *                      potentials of rows of count 0 included; potentials may be NULL.
+ * One launch per step, n_sinkhorn + 1 in all; a step costs one float64 exp per replicate and pooled pair.  The order of every sum
+ * depends on (nr, nf, d) only, so a replicate's outputs are bitwise the same alone, in any group, in any call.  value [reps],
+ * drift [reps], potentials [reps, 2, nr + nf]; every element is written.
+ * PFM_EINVAL for bad sizes, reps > 65535, an eps that is not positive and finite (or whose reciprocal is not), n_sinkhorn < 0 or
+ * above 1000000; PFM_EUNSUPPORTED for a p other than 1 or 2; on any error nothing is written.
+ */
+int pfm_sinkhorn(void *stream, const double *Xr, int64_t nr, const double *Xf, int64_t nf, int64_t d,
+                 const int32_t *idx_r, const int32_t *idx_f, int64_t reps, int p, double eps, int64_t n_sinkhorn,
+                 double *value, double *drift, double *potentials, void *workspace, size_t workspace_bytes);
 
 /* ---- permutation two-sample tests (pf_perm.hip) -------------------------------------------------- */
 
