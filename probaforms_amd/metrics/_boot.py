@@ -1,11 +1,12 @@
-"""Host side shared by the two bootstrapped metrics: argument checks, the float64 device copies, the
-StandardScaler step, and the bootstrap index stream of the reference.
+"""Host side shared by the bootstrapped metrics: argument checks, the float64 device copies, the
+StandardScaler step, the bootstrap index stream of the reference, and the one driver of a call's replicates.
 
 The reference resamples with `sklearn.utils.resample(X)` (mmd.py:54-55, fd.py:41-42), which on numpy's
 global legacy generator draws `randint(0, n, size=n)`; per iteration X's indices first, then Y's.  The
 same draws are made here, in the same order, so the generator ends where the reference leaves it.
 Replicates run in groups whose indices are drawn on the host, uploaded as int32 and consumed by the
-kernels; the next group is drawn while the current group's kernels run.
+kernels; the next group is drawn while the current group's kernels run.  replicates() is what a metric
+calls: it sizes the groups and the workspace, and runs either the drawn replicates or the identity one.
 """
 import numpy as np
 import torch
@@ -35,15 +36,15 @@ def _check_2d(A, name):
     return A, shape
 
 
-def prepare(A, B, names, n_iters):
-    """-> (A, B) as contiguous float64 tensors on one HIP device.  A CUDA tensor stays on its device
-    (float32 is upcast there); anything else is converted with numpy and uploaded."""
+def prepare(A, B, names, n_iters, standardize=False):
+    """-> (A, B) as contiguous float64 tensors on one HIP device, standardized there if asked.  A CUDA tensor
+    stays on its device (float32 is upcast there); anything else is converted with numpy and uploaded."""
+    from . import _m1d                    # (imports this module)
     A, sa = _check_2d(A, names[0])
     B, sb = _check_2d(B, names[1])
     if sa[1] != sb[1]:
         raise ValueError("%s and %s have different numbers of features: %d and %d" % (names[0], names[1], sa[1], sb[1]))
-    if isinstance(n_iters, bool) or not isinstance(n_iters, (int, np.integer)) or n_iters < 1:
-        raise ValueError("n_iters must be a positive integer, got %r" % (n_iters,))
+    _m1d.check_positive_int(n_iters, "n_iters")
     if not torch.cuda.is_available():
         raise RuntimeError("probaforms_amd.metrics runs on a HIP device and none is visible (there is no CPU fallback)")
     dev = None
@@ -58,7 +59,11 @@ def prepare(A, B, names, n_iters):
         if not isinstance(t, torch.Tensor):
             t = torch.from_numpy(np.ascontiguousarray(t, dtype=np.float64))
         return t.detach().to(device=dev, dtype=torch.float64).contiguous()
-    return dev64(A), dev64(B)
+    A, B = dev64(A), dev64(B)
+    if standardize:
+        with torch.cuda.device(dev):
+            A, B = globals()["standardize"](A, B)      # (the argument shadows the function)
+    return A, B
 
 
 def standardize(A, B):
@@ -113,3 +118,24 @@ def run_groups(n_iters, na, nb, device, launch, ws_per_rep=0):
         done[k] = torch.cuda.Event()
         done[k].record(stream)
         launch(start, reps, d[:reps * na], d[reps * na:])
+
+
+def replicates(na, nb, device, n_iters, workspace_bytes, launch, ws_per_rep=None):
+    """The replicates of one call on samples of na and nb rows: launch(start, reps, idx_a, idx_b, ws) enqueues
+    replicates start .. start + reps - 1 from their int32 indices [reps, na] and [reps, nb], with the
+    workspace ws of workspace_bytes(reps) bytes at least (the metric's own size function of a group's replicate
+    count).  The groups are run_groups', sized by ws_per_rep: workspace_bytes(1) unless the metric counts
+    other bytes per replicate.  The first group is the largest.
+    n_iters = None is the identity replicate, the samples as given: one launch, nothing is drawn from numpy's
+    generator and no pinned buffer is made."""
+    def empty(nbytes):
+        return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+    if n_iters is None:
+        ia, ib = (torch.arange(n, dtype=torch.int32, device=device) for n in (na, nb))
+        launch(0, 1, ia, ib, empty(workspace_bytes(1)))
+        return
+    if ws_per_rep is None:
+        ws_per_rep = workspace_bytes(1)
+    ws = empty(max(workspace_bytes(r) for r in group_sizes(n_iters, na + nb, ws_per_rep)))
+    run_groups(n_iters, na, nb, device, lambda start, reps, ia, ib: launch(start, reps, ia, ib, ws), ws_per_rep)

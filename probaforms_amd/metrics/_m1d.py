@@ -3,7 +3,7 @@ groups of each pooled feature, the replicate groups of pfm_metric1d, and the ref
 
 The reference (probaforms/metrics/ks1d.py, _bootstrap_metric) resamples X_real, then X_fake, with
 sklearn.utils.resample per iteration, scores every feature with a 1-D two-sample function and averages the
-features as `score += mval / n_dim`.  The draws are _boot.run_groups'; the kernels return the rank and density
+features as `score += mval / n_dim`.  The draws are _boot.replicates'; the kernels return the rank and density
 sums of every (replicate, feature) and the scalar expressions of scipy / sklearn / the reference are applied here
 in numpy, in the reference's order, so that KS, CvM and the histogram divergences are bitwise the reference's.
 """
@@ -18,6 +18,33 @@ from . import _boot, _lib
 _NO_BINS = object()
 
 
+# ---- the scalar checks of every metric's arguments (each caller's message names its parameter) ----------------
+
+def is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+
+def check_positive_int(v, name):
+    if not is_int(v) or v < 1:
+        raise ValueError("%s must be a positive integer, got %r" % (name, v))
+    return int(v)
+
+
+def check_bool(v, name):
+    if not isinstance(v, (bool, np.bool_)):
+        raise ValueError("%s must be a bool, got %r" % (name, v))
+
+
+def check_positive(v, name, none_ok=False, reciprocal=False):
+    """a positive finite int or float (no bool); reciprocal: 1 / v is finite as well; none_ok: or None"""
+    if v is None and none_ok:
+        return
+    ok = isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
+    if not ok or not (math.isfinite(v) and v > 0 and (not reciprocal or math.isfinite(1.0 / float(v)))):
+        raise ValueError("%s must be %sa positive finite number%s, got %r"
+                         % (name, "None or " if none_ok else "", " with a finite reciprocal" if reciprocal else "", v))
+
+
 def check_args(X_real, X_fake, n_iters, bins=_NO_BINS):
     """what is checked before any draw and without a device: shapes, dtypes, finiteness, n_iters, bins (if given)"""
     names = ("X_real", "X_fake")
@@ -30,10 +57,9 @@ def check_args(X_real, X_fake, n_iters, bins=_NO_BINS):
         shapes.append(shape)
     if shapes[0][1] != shapes[1][1]:
         raise ValueError("X_real and X_fake have different numbers of features: %d and %d" % (shapes[0][1], shapes[1][1]))
-    if isinstance(n_iters, bool) or not isinstance(n_iters, (int, np.integer)) or n_iters < 1:
-        raise ValueError("n_iters must be a positive integer, got %r" % (n_iters,))
-    if bins is not _NO_BINS and (isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or bins < 1):
-        raise ValueError("bins must be a positive integer, got %r" % (bins,))
+    check_positive_int(n_iters, "n_iters")
+    if bins is not _NO_BINS:
+        check_positive_int(bins, "bins")
 
 
 class Pooled:
@@ -79,18 +105,14 @@ def run(metric, X_real, X_fake, n_iters, bins=1, bandwidths=(1.0, 1.0)):
     with torch.cuda.device(Xr.device):
         p = Pooled(Xr, Xf)
         nr, nf, d = p.nr, p.nf, p.d
-        per_rep = _lib.metric1d_workspace_bytes(metric, nr, nf, d, 1, bins)
-        sizes = _boot.group_sizes(n_iters, nr + nf, per_rep)
-        ws = torch.empty(max(_lib.metric1d_workspace_bytes(metric, nr, nf, d, r, bins) for r in sizes),
-                         dtype=torch.uint8, device=p.device)
         tail, dtype = OUT_SHAPE[metric]
         out = torch.empty((n_iters, d) + tuple(bins if t is None else t for t in tail), dtype=dtype, device=p.device)
 
-        def launch(start, reps, ir, jf):
+        def launch(start, reps, ir, jf, ws):
             _lib.metric1d(metric, p.cols, p.perm, p.gstart, p.ngroups, nr, nf, ir, jf, reps, bins, bandwidths[0],
                           bandwidths[1], out[start:start + reps], ws)
 
-        _boot.run_groups(n_iters, nr, nf, p.device, launch, per_rep)
+        _boot.replicates(nr, nf, p.device, n_iters, lambda r: _lib.metric1d_workspace_bytes(metric, nr, nf, d, r, bins), launch)
         return out.cpu().numpy()
 
 

@@ -145,20 +145,12 @@ __global__ void __launch_bounds__(NT) k_energy_tiles(const double *Xr, int64_t n
     waves_to_partial(sh.u.red, nrep, partial + wg * reps + rep0);
 }
 
-bool energy_args_ok(int64_t nr, int64_t nf, int64_t d, int64_t reps) {
-    if (nr < 1 || nf < 1 || d < 1 || reps < 1 || reps > 65535) return false;
-    if (nr > (int64_t)INT32_MAX || nf > (int64_t)INT32_MAX) return false;        // int32 indices
-    const int64_t big = nr > nf ? nr : nf;
-    if (d > INT64_MAX / big / (int64_t)sizeof(double)) return false;            // a row's byte offset overflows
-    return true;
-}
-
 }  // namespace
 
 // ---- C ABI --------------------------------------------------------------------------------------------
 
 extern "C" size_t pfm_energy_workspace_bytes(int64_t nr, int64_t nf, int64_t d, int64_t reps) {
-    if (!energy_args_ok(nr, nf, d, reps)) return 0;
+    if (!pair_sizes_ok(nr, nf, d, reps)) return 0;
     const Plan p = plan_of(nr, nf);
     return align256(sizeof(int32_t) * (size_t)reps * (size_t)(nr + nf)) +
            align256(sizeof(double) * (size_t)reps * (size_t)p.first[3]);
@@ -167,21 +159,15 @@ extern "C" size_t pfm_energy_workspace_bytes(int64_t nr, int64_t nf, int64_t d, 
 extern "C" int pfm_energy(void *stream, const double *Xr, int64_t nr, const double *Xf, int64_t nf, int64_t d,
                           const int32_t *idx_r, const int32_t *idx_f, int64_t reps, double *sums, void *workspace,
                           size_t workspace_bytes) {
-    if (!Xr || !Xf || !idx_r || !idx_f || !sums || !energy_args_ok(nr, nf, d, reps)) return PFM_EINVAL;
+    if (!Xr || !Xf || !idx_r || !idx_f || !sums || !pair_sizes_ok(nr, nf, d, reps)) return PFM_EINVAL;
     const size_t need = pfm_energy_workspace_bytes(nr, nf, d, reps);
     if (!workspace || workspace_bytes < need) return PFM_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const Plan p = plan_of(nr, nf);
-    const int64_t N = nr + nf;
-    const size_t cbytes = sizeof(int32_t) * (size_t)reps * (size_t)N;
     int32_t *cnt = (int32_t *)workspace;
-    double *partial = (double *)((char *)workspace + align256(cbytes));
+    double *partial = (double *)((char *)workspace + align256(sizeof(int32_t) * (size_t)reps * (size_t)(nr + nf)));
 
-    PFM_TRY(hipMemsetAsync(cnt, 0, cbytes, st));
-    int64_t cb = (N + NT - 1) / NT;
-    if (cb > 1024) cb = 1024;
-    hipLaunchKernelGGL(k_counts, dim3((unsigned)cb, (unsigned)reps), dim3(NT), 0, st, idx_r, idx_f, nr, nf, cnt);
-    PFM_TRY(hipGetLastError());
+    PFM_TRY(launch_counts(st, idx_r, idx_f, nr, nf, reps, cnt));
     const dim3 grid((unsigned)p.first[3], (unsigned)((reps + SUPER - 1) / SUPER));
     hipLaunchKernelGGL(k_energy_tiles, grid, dim3(NT), 0, st, Xr, nr, Xf, nf, d, (const int32_t *)cnt, reps, p, partial);
     PFM_TRY(hipGetLastError());

@@ -20,7 +20,7 @@
 #include <stdint.h>
 
 #include "pf_metrics.h"
-#include "pf_pairtile.h"
+#include "pf_nearest.h"
 
 namespace {
 
@@ -31,31 +31,8 @@ struct Rows {                       // one replicate's resampled sample X[idx]: 
     __device__ const double *row(int64_t r) const { return X + (int64_t)idx[r] * d; }
 };
 
-// v into the ascending list b of the L smallest values seen (the caller has tested v < b[L - 1]): it replaces the largest
-// and sinks through an unrolled compare-exchange chain; every index is a compile-time constant, so b stays in registers
-template <int L>
-__device__ inline void push(double (&b)[L], double v) {
-    b[L - 1] = v;
-#pragma unroll
-    for (int i = L - 1; i > 0; --i) {
-        const double hi = b[i], lo = b[i - 1];
-        const bool sw = hi < lo;
-        b[i - 1] = sw ? hi : lo;
-        b[i] = sw ? lo : hi;
-    }
-}
-
-template <int L>
-__device__ inline void pop(double (&b)[L]) {
-#pragma unroll
-    for (int i = 0; i + 1 < L; ++i) b[i] = b[i + 1];
-    b[L - 1] = INFINITY;
-}
-
-// L >= k + 1 values are kept per (thread, query row).  A thread tests a candidate against `bound`, an upper bound of the
-// row's (k + 1)-th smallest value: the smallest of the 16 threads' current largest kept values (any one list already holds
-// L >= k + 1 values no larger), shared among the 16 lanes of the row after every tile.  A value not below the bound cannot
-// change the (k + 1)-th smallest, so skipping it changes nothing, and the chain is rarely entered.
+// The sweep of pf_nearest.h over the candidate tiles of the same resampled sample, values only: every row in range counts, the
+// query row itself included, so L >= k + 1 values are kept and round k of the merge gives the (k + 1)-th smallest of the row.
 template <int L>
 __global__ void __launch_bounds__(NT) k_knn_radius(const double *Xr, int64_t nr, const double *Xf, int64_t nf, int64_t d,
                                                    const int32_t *idx_r, const int32_t *idx_f, int k, double *rad_r,
@@ -73,13 +50,8 @@ __global__ void __launch_bounds__(NT) k_knn_radius(const double *Xr, int64_t nr,
     double *out = fake ? rad_f + rep * nf : rad_r + rep * nr;
     const int tid = threadIdx.x, ti = tid >> 4, tj = tid & 15;
 
-    double best[4][L], bound[4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-        bound[a] = INFINITY;
-#pragma unroll
-        for (int i = 0; i < L; ++i) best[a][i] = INFINITY;
-    }
+    Nearest<L, false> near;
+    near.init();
     const bool resident = d <= DC;
     if (resident) stage(S, bi * TILE, 0, (int)d, sA);     // (tile_d2 begins with a barrier)
     const int64_t nb = tiles_per_side(S.n);
@@ -90,47 +62,12 @@ __global__ void __launch_bounds__(NT) k_knn_radius(const double *Xr, int64_t nr,
         for (int b = 0; b < 4; ++b) {
             const bool in = bj * TILE + tj + 16 * b < S.n;
 #pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                const double v = in ? acc[a][b] : INFINITY;
-                if (v < bound[a]) {
-                    push<L>(best[a], v);
-                    bound[a] = best[a][L - 1] < bound[a] ? best[a][L - 1] : bound[a];
-                }
-            }
+            for (int a = 0; a < 4; ++a) near.offer(a, in ? acc[a][b] : INFINITY, 0);
         }
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            double m = bound[a];
-#pragma unroll
-            for (int s = 1; s < 16; s <<= 1) {
-                const double o = __shfl_xor(m, s, 16);
-                m = o < m ? o : m;
-            }
-            bound[a] = m;
-        }
+        near.share();
     }
-
-    // the 16 threads of a query row merge their ascending lists through LDS: k + 1 rounds, each takes the smallest of the
-    // 16 heads (the lowest thread among equals pops it); the value taken in round k is the (k + 1)-th smallest of the row
     double res[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int it = 0; it <= k; ++it) {
-        double (*h)[16][16] = heads[it & 1];
-#pragma unroll
-        for (int a = 0; a < 4; ++a) h[a][ti][tj] = best[a][0];
-        __syncthreads();
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            double m = h[a][ti][0];
-            int w = 0;
-#pragma unroll
-            for (int t = 1; t < 16; ++t) {
-                const double o = h[a][ti][t];
-                if (o < m) { m = o; w = t; }
-            }
-            res[a] = m;
-            if (w == tj) pop<L>(best[a]);
-        }
-    }
+    for (int it = 0; it <= k; ++it) near.take(heads[it & 1], nullptr, [&](int a, double m, int32_t) { res[a] = m; });
     if (tj == 0) {
 #pragma unroll
         for (int a = 0; a < 4; ++a) {

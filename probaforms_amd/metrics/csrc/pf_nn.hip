@@ -4,64 +4,23 @@
 //   k_nn_index<L>   one workgroup per 64-row query tile of the pooled sample Z: it sweeps every 64-row candidate tile in
 //                   ascending order and writes, per query row a, the k nearest OTHER rows in ascending order of
 //                   (d^2, row index), as nbr[a, r] and d2[a, r].  Row a itself is left out by its index, not by its distance:
-//                   a duplicate of a is a neighbour at distance exactly 0.  k_knn_radius<L> of pf_knn.hip with the index kept
-//                   beside the value, in the lists and in the merge.
+//                   a duplicate of a is a neighbour at distance exactly 0.  The sweep of pf_nearest.h with the index kept
+//                   beside the value (which also says why its pruning is exact under that order).
 //   k_nn_count      workgroups (labelling, slice of the n k slots): the labelling's bytes are packed into bits in LDS (while
 //                   n <= PFM_NN_STAGE_MAX_N; read from global memory above that), nbr is read coalesced, and the slots whose
 //                   row and neighbour are both labelled (counts[p, 0]) or both unlabelled (counts[p, 1]) are counted
 //   k_nn_count_sum  adds the slices' counts of a labelling where there are several
 // Every distance is tile_d2 of pf_pairtile.h on a Plain source: bitwise what pfm_prdc and the other kernels form for the pair.
 // The counts are integers added in a fixed order.  Both calls are bitwise reproducible and keep no state.
-//
-// Why `v < bound` stays exact under the (d^2, row index) order.  A lane keeps, per query row, the L >= k smallest candidates it
-// has met, ascending.  It meets its candidates in ascending row index: the tiles are swept in ascending order and inside a tile
-// the lane's columns tj + 16 b ascend with b.  The insertion moves a new entry past strictly larger values only, so among equal
-// values the earlier, smaller index stays in front: a list is ascending in (d^2, index).  `bound` is never above the lane's own
-// L-th value, and is lowered after every tile to the smallest L-th value among the row's 16 lanes.  So whatever the bound rests
-// on is a list of L >= k candidates that were met before the candidate under test: by the lane itself (smaller indices, same
-// or earlier tile) or by another lane in an EARLIER tile (smaller indices again).  A candidate with v >= bound therefore has at
-// least k candidates in front of it in (d^2, index) order, all with values <= v and smaller indices; it is not among the k
-// nearest and skipping it changes nothing, ties included.  The argument needs the ascending sweep: in another order a
-// candidate equal to the bound could carry the smaller index and would have to be kept.
 #include <hip/hip_runtime.h>
 
 #include <math.h>
 #include <stdint.h>
 
 #include "pf_metrics.h"
-#include "pf_pairtile.h"
+#include "pf_nearest.h"
 
 namespace {
-
-// (v, j) into the list (b, id), ascending in (value, index), of the L nearest candidates met so far (the caller has tested
-// v < b[L - 1], and j is above every index in the list): it replaces the last entry and sinks past strictly larger values
-// through an unrolled compare-exchange chain; every list index is a compile-time constant, so the lists stay in registers
-template <int L>
-__device__ inline void push(double (&b)[L], int32_t (&id)[L], double v, int32_t j) {
-    b[L - 1] = v;
-    id[L - 1] = j;
-#pragma unroll
-    for (int i = L - 1; i > 0; --i) {
-        const double hi = b[i], lo = b[i - 1];
-        const int32_t jh = id[i], jl = id[i - 1];
-        const bool sw = hi < lo;
-        b[i - 1] = sw ? hi : lo;
-        b[i] = sw ? lo : hi;
-        id[i - 1] = sw ? jh : jl;
-        id[i] = sw ? jl : jh;
-    }
-}
-
-template <int L>
-__device__ inline void pop(double (&b)[L], int32_t (&id)[L]) {
-#pragma unroll
-    for (int i = 0; i + 1 < L; ++i) {
-        b[i] = b[i + 1];
-        id[i] = id[i + 1];
-    }
-    b[L - 1] = INFINITY;
-    id[L - 1] = INT32_MAX;
-}
 
 template <int L>
 __global__ void __launch_bounds__(NT) k_nn_index(const double *Zp, int64_t n, int64_t d, int k, int32_t *nbr, double *d2) {
@@ -75,17 +34,8 @@ __global__ void __launch_bounds__(NT) k_nn_index(const double *Zp, int64_t n, in
     Z.d = d;
     const int tid = threadIdx.x, ti = tid >> 4, tj = tid & 15;
 
-    double best[4][L], bound[4];
-    int32_t who[4][L];
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-        bound[a] = INFINITY;
-#pragma unroll
-        for (int i = 0; i < L; ++i) {
-            best[a][i] = INFINITY;
-            who[a][i] = INT32_MAX;
-        }
-    }
+    Nearest<L, true> near;
+    near.init();
     const bool resident = d <= DC;
     if (resident) stage(Z, bi * TILE, 0, (int)d, sA);     // (tile_d2 begins with a barrier)
     const int64_t nb = tiles_per_side(n);
@@ -98,53 +48,19 @@ __global__ void __launch_bounds__(NT) k_nn_index(const double *Zp, int64_t n, in
 #pragma unroll
             for (int a = 0; a < 4; ++a) {
                 const bool take = gj < n && gj != bi * TILE + ti + 16 * a;      // a row is no neighbour of itself
-                const double v = take ? acc[a][b] : INFINITY;
-                if (v < bound[a]) {
-                    push<L>(best[a], who[a], v, (int32_t)gj);
-                    bound[a] = best[a][L - 1] < bound[a] ? best[a][L - 1] : bound[a];
-                }
+                near.offer(a, take ? acc[a][b] : INFINITY, (int32_t)gj);
             }
         }
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            double m = bound[a];
-#pragma unroll
-            for (int s = 1; s < 16; s <<= 1) {
-                const double o = __shfl_xor(m, s, 16);
-                m = o < m ? o : m;
-            }
-            bound[a] = m;
-        }
+        near.share();
     }
-
-    // the 16 threads of a query row merge their lists through LDS: k rounds, each takes the smallest (d^2, index) of the 16
-    // heads, and the thread that held it pops it (an index is in one list only); round r gives the neighbour of rank r
-    for (int it = 0; it < k; ++it) {
-        double (*h)[16][16] = heads[it & 1];
-        int32_t (*hj)[16][16] = headj[it & 1];
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            h[a][ti][tj] = best[a][0];
-            hj[a][ti][tj] = who[a][0];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            double m = h[a][ti][0];
-            int32_t mj = hj[a][ti][0];
-#pragma unroll
-            for (int t = 1; t < 16; ++t) {
-                const double o = h[a][ti][t];
-                const int32_t oj = hj[a][ti][t];
-                if (o < m || (o == m && oj < mj)) { m = o; mj = oj; }
-            }
-            if (mj == who[a][0]) pop<L>(best[a], who[a]);
+    for (int it = 0; it < k; ++it) {            // round r of the merge gives the neighbour of rank r
+        near.take(heads[it & 1], headj[it & 1], [&](int a, double m, int32_t mj) {
             const int64_t gi = bi * TILE + ti + 16 * a;
             if (tj == 0 && gi < n) {
                 nbr[gi * k + it] = mj;
                 d2[gi * k + it] = m;
             }
-        }
+        });
     }
 }
 

@@ -1,5 +1,6 @@
 // pf_scan1d.h -- what the per-column bootstrap kernels of libpf_metrics.so share (pf_metrics1d.hip, pf_wasserstein.hip): the
 // draw counts of a replicate, a column's sorted order with its tie groups, and the workgroup's integer scan and fixed-order sum.
+// The draw counts (launch_counts) also serve pf_energy.hip and pf_sinkhorn.hip, whose size check pair_sizes_ok is.
 #ifndef PF_SCAN1D_H
 #define PF_SCAN1D_H
 
@@ -22,6 +23,26 @@ __global__ void __launch_bounds__(NT) k_counts(const int32_t *idx_r, const int32
             if ((uint32_t)j < (uint32_t)nf) atomicAdd(&c[nr + j], 1);
         }
     }
+}
+
+// cnt [reps, nr + nf] = the draw counts of every replicate: zeroed and counted on `stream`; the launch's status
+inline hipError_t launch_counts(hipStream_t stream, const int32_t *idx_r, const int32_t *idx_f, int64_t nr, int64_t nf,
+                                int64_t reps, int32_t *cnt) {
+    const int64_t N = nr + nf;
+    const hipError_t e = hipMemsetAsync(cnt, 0, sizeof(int32_t) * (size_t)reps * (size_t)N, stream);
+    if (e != hipSuccess) return e;
+    int64_t cb = (N + NT - 1) / NT;
+    if (cb > 1024) cb = 1024;
+    hipLaunchKernelGGL(k_counts, dim3((unsigned)cb, (unsigned)reps), dim3(NT), 0, stream, idx_r, idx_f, nr, nf, cnt);
+    return hipGetLastError();
+}
+
+// the sizes pfm_energy and pfm_sinkhorn accept: two samples of d features gathered through int32 indices, reps in grid.y
+inline bool pair_sizes_ok(int64_t nr, int64_t nf, int64_t d, int64_t reps) {
+    if (nr < 1 || nf < 1 || d < 1 || reps < 1 || reps > 65535) return false;
+    if (nr > (int64_t)INT32_MAX || nf > (int64_t)INT32_MAX) return false;        // int32 indices
+    const int64_t big = nr > nf ? nr : nf;
+    return d <= INT64_MAX / big / (int64_t)sizeof(double);                      // a row's byte offset overflows
 }
 
 struct Feature {                 // one (feature, replicate): the sorted order, its tie groups, the draw counts

@@ -183,14 +183,6 @@ __global__ void __launch_bounds__(NT) k_sinkhorn_finish(const int32_t *__restric
         for (int64_t i = tid; i < 2 * N; i += NT) potentials[rep * 2 * N + i] = f[i];
 }
 
-bool sinkhorn_sizes_ok(int64_t nr, int64_t nf, int64_t d, int64_t reps) {
-    if (nr < 1 || nf < 1 || d < 1 || reps < 1 || reps > 65535) return false;
-    if (nr > (int64_t)INT32_MAX || nf > (int64_t)INT32_MAX) return false;        // int32 indices
-    const int64_t big = nr > nf ? nr : nf;
-    if (d > INT64_MAX / big / (int64_t)sizeof(double)) return false;            // a row's byte offset overflows
-    return true;
-}
-
 struct Layout {                     // the workspace: draw counts, log-weights, three potential buffers
     size_t cnt, lw, pot, total;     // bytes of the counts, of the log-weights, of ONE potential buffer, of everything
 };
@@ -210,14 +202,14 @@ Layout layout_of(int64_t nr, int64_t nf, int64_t reps) {
 // ---- C ABI --------------------------------------------------------------------------------------------
 
 extern "C" size_t pfm_sinkhorn_workspace_bytes(int64_t nr, int64_t nf, int64_t d, int64_t reps) {
-    if (!sinkhorn_sizes_ok(nr, nf, d, reps)) return 0;
+    if (!pair_sizes_ok(nr, nf, d, reps)) return 0;
     return layout_of(nr, nf, reps).total;
 }
 
 extern "C" int pfm_sinkhorn(void *stream, const double *Xr, int64_t nr, const double *Xf, int64_t nf, int64_t d,
                             const int32_t *idx_r, const int32_t *idx_f, int64_t reps, int p, double eps, int64_t n_sinkhorn,
                             double *value, double *drift, double *potentials, void *workspace, size_t workspace_bytes) {
-    if (!Xr || !Xf || !idx_r || !idx_f || !value || !drift || !sinkhorn_sizes_ok(nr, nf, d, reps)) return PFM_EINVAL;
+    if (!Xr || !Xf || !idx_r || !idx_f || !value || !drift || !pair_sizes_ok(nr, nf, d, reps)) return PFM_EINVAL;
     if (!(eps > 0.0) || !isfinite(eps) || !isfinite(1.0 / eps) || n_sinkhorn < 0 || n_sinkhorn > MAX_SINKHORN)
         return PFM_EINVAL;
     if (p != 1 && p != 2) return PFM_EUNSUPPORTED;
@@ -231,12 +223,8 @@ extern "C" int pfm_sinkhorn(void *stream, const double *Xr, int64_t nr, const do
     double *pot[3];
     for (int k = 0; k < 3; ++k) pot[k] = (double *)(base + l.cnt + l.lw + k * l.pot);
 
-    PFM_TRY(hipMemsetAsync(cnt, 0, sizeof(int32_t) * (size_t)reps * (size_t)N, st));
     PFM_TRY(hipMemsetAsync(pot[0], 0, sizeof(double) * 2 * (size_t)reps * (size_t)N, st));   // every potential starts at 0
-    int64_t cb = (N + NT - 1) / NT;
-    if (cb > 1024) cb = 1024;
-    hipLaunchKernelGGL(k_counts, dim3((unsigned)cb, (unsigned)reps), dim3(NT), 0, st, idx_r, idx_f, nr, nf, cnt);
-    PFM_TRY(hipGetLastError());
+    PFM_TRY(launch_counts(st, idx_r, idx_f, nr, nf, reps, cnt));
     int64_t lb = (reps * N + NT - 1) / NT;
     if (lb > 4096) lb = 4096;
     hipLaunchKernelGGL(k_logw, dim3((unsigned)lb), dim3(NT), 0, st, (const int32_t *)cnt, nr, nf, reps, lw);

@@ -323,11 +323,7 @@ extern "C" int pfm_wasserstein1d(void *stream, int p, const double *cols, const 
     double *ws_val = (double *)tables;
     int32_t *ws_cum = (int32_t *)(tables + align256(sizeof(double) * reps * d * N));
 
-    PFM_TRY(hipMemsetAsync(cnt, 0, sizeof(int32_t) * reps * N, st));
-    int64_t cb = (N + NT - 1) / NT;
-    if (cb > 1024) cb = 1024;
-    hipLaunchKernelGGL(k_counts, dim3((unsigned)cb, (unsigned)reps), dim3(NT), 0, st, idx_r, idx_f, nr, nf, cnt);
-    PFM_TRY(hipGetLastError());
+    PFM_TRY(launch_counts(st, idx_r, idx_f, nr, nf, reps, cnt));
 
     const dim3 grid((unsigned)d, (unsigned)reps);
     if (p == 1)

@@ -26,17 +26,8 @@ from . import _boot, _lib, _m1d
 
 def _check(X_real, X_fake, n_iters, standardize, squared):
     _m1d.check_args(X_real, X_fake, n_iters)
-    for v, name in ((standardize, "standardize"), (squared, "squared")):
-        if not isinstance(v, (bool, np.bool_)):
-            raise ValueError("%s must be a bool, got %r" % (name, v))
-
-
-def _prepare(X_real, X_fake, n_iters, standardize):
-    Xr, Xf = _boot.prepare(X_real, X_fake, ("X_real", "X_fake"), n_iters)
-    if standardize:
-        with torch.cuda.device(Xr.device):
-            Xr, Xf = _boot.standardize(Xr, Xf)
-    return Xr, Xf
+    _m1d.check_bool(standardize, "standardize")
+    _m1d.check_bool(squared, "squared")
 
 
 def means_of(S, nr, nf):
@@ -51,23 +42,26 @@ def values_of(E, squared):
     return d2 if squared else np.sqrt(np.maximum(d2, 0.0))
 
 
+def _means(X_real, X_fake, n_iters, standardize):
+    """the checked arguments -> numpy float64 [n_iters, 3] exx, eyy, exy; n_iters = None: [1, 3] of the samples as given"""
+    n = 1 if n_iters is None else n_iters
+    Xr, Xf = _boot.prepare(X_real, X_fake, ("X_real", "X_fake"), n, standardize)
+    (nr, d), nf = Xr.shape, Xf.shape[0]
+    with torch.cuda.device(Xr.device):
+        sums = torch.empty((n, 3), dtype=torch.float64, device=Xr.device)
+
+        def launch(start, reps, ir, jf, ws):
+            _lib.energy(Xr, Xf, ir, jf, reps, sums[start:start + reps], ws)
+
+        _boot.replicates(nr, nf, Xr.device, n_iters, lambda r: _lib.energy_workspace_bytes(nr, nf, d, r), launch)
+        return means_of(sums.cpu().numpy(), nr, nf)
+
+
 def _replicates(X_real, X_fake, n_iters=100, standardize=False):
     """-> numpy float64 [n_iters, 3]: exx, eyy, exy of every bootstrap replicate, the draws made from numpy's global
     generator as the reference's metrics make them"""
     _check(X_real, X_fake, n_iters, standardize, False)
-    Xr, Xf = _prepare(X_real, X_fake, n_iters, standardize)
-    (nr, d), nf = Xr.shape, Xf.shape[0]
-    with torch.cuda.device(Xr.device):
-        per_rep = _lib.energy_workspace_bytes(nr, nf, d, 1)
-        sizes = _boot.group_sizes(n_iters, nr + nf, per_rep)
-        ws = torch.empty(max(_lib.energy_workspace_bytes(nr, nf, d, r) for r in sizes), dtype=torch.uint8, device=Xr.device)
-        sums = torch.empty((n_iters, 3), dtype=torch.float64, device=Xr.device)
-
-        def launch(start, reps, ir, jf):
-            _lib.energy(Xr, Xf, ir, jf, reps, sums[start:start + reps], ws)
-
-        _boot.run_groups(n_iters, nr, nf, Xr.device, launch, per_rep)
-        return means_of(sums.cpu().numpy(), nr, nf)
+    return _means(X_real, X_fake, n_iters, standardize)
 
 
 # per-replicate values of the public call, on the same draws: float64 [n_iters, 3] (exx, eyy, exy)
@@ -115,12 +109,4 @@ def energy_distance_full_sample(X_real, X_fake, standardize=False, squared=False
     The distance, numpy float64.
     '''
     _check(X_real, X_fake, 1, standardize, squared)
-    Xr, Xf = _prepare(X_real, X_fake, 1, standardize)
-    (nr, d), nf = Xr.shape, Xf.shape[0]
-    with torch.cuda.device(Xr.device):
-        ws = torch.empty(_lib.energy_workspace_bytes(nr, nf, d, 1), dtype=torch.uint8, device=Xr.device)
-        sums = torch.empty((1, 3), dtype=torch.float64, device=Xr.device)
-        ir = torch.arange(nr, dtype=torch.int32, device=Xr.device)
-        jf = torch.arange(nf, dtype=torch.int32, device=Xr.device)
-        _lib.energy(Xr, Xf, ir, jf, 1, sums, ws)
-        return values_of(means_of(sums.cpu().numpy(), nr, nf), squared)[0]
+    return values_of(_means(X_real, X_fake, None, standardize), squared)[0]

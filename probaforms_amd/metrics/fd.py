@@ -56,22 +56,17 @@ def replicates(X_real, X_fake, n_iters=100, standardize=False):
 
 def moments(X_real, X_fake, n_iters=100, standardize=False):
     """-> (mean [n_iters, 2, d], cov [n_iters, 2, d, d]) of the resampled real (0) and fake (1) sets, numpy float64"""
-    Xr, Xf = _boot.prepare(X_real, X_fake, ("X_real", "X_fake"), n_iters)
+    Xr, Xf = _boot.prepare(X_real, X_fake, ("X_real", "X_fake"), n_iters, standardize)
     nr, d = Xr.shape
     nf = Xf.shape[0]
     if d > _lib.MOMENTS_MAX_D:
         raise ValueError("frechet_distance supports at most %d features, got %d" % (_lib.MOMENTS_MAX_D, d))
     with torch.cuda.device(Xr.device):
-        if standardize:
-            Xr, Xf = _boot.standardize(Xr, Xf)
-        per_rep = _lib.moments_workspace_bytes(nr, nf, d, 1)
-        sizes = _boot.group_sizes(n_iters, nr + nf, per_rep)
-        ws = torch.empty(max(_lib.moments_workspace_bytes(nr, nf, d, r) for r in sizes), dtype=torch.uint8, device=Xr.device)
         mean = torch.empty((n_iters, 2, d), dtype=torch.float64, device=Xr.device)
         cov = torch.empty((n_iters, 2, d, d), dtype=torch.float64, device=Xr.device)
 
-        def launch(start, reps, ir, jf):
+        def launch(start, reps, ir, jf, ws):
             _lib.boot_moments(Xr, Xf, ir, jf, reps, mean[start:start + reps], cov[start:start + reps], ws)
 
-        _boot.run_groups(n_iters, nr, nf, Xr.device, launch, per_rep)
+        _boot.replicates(nr, nf, Xr.device, n_iters, lambda r: _lib.moments_workspace_bytes(nr, nf, d, r), launch)
         return mean.cpu().numpy(), cov.cpu().numpy()

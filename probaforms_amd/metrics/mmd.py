@@ -40,19 +40,16 @@ def maximum_mean_discrepancy(X, Y, n_iters=100, standardize=False):
 
 def replicates(X, Y, n_iters=100, standardize=False):
     """-> (medians, mmds): numpy float64 per replicate, the draws of the public call (a median of 0 gives a NaN mmd)"""
-    X, Y = _boot.prepare(X, Y, ("X", "Y"), n_iters)
+    X, Y = _boot.prepare(X, Y, ("X", "Y"), n_iters, standardize)
     with torch.cuda.device(X.device):
-        if standardize:
-            X, Y = _boot.standardize(X, Y)
         nx, d = X.shape
         ny = Y.shape[0]
-        ws_bytes = max(_lib.mmd_workspace_bytes(nx, ny, d, r) for r in _boot.group_sizes(n_iters, nx + ny))
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=X.device)
         med = torch.empty(n_iters, dtype=torch.float64, device=X.device)
         out = torch.empty(n_iters, dtype=torch.float64, device=X.device)
 
-        def launch(start, reps, ix, iy):
+        def launch(start, reps, ix, iy, ws):
             _lib.mmd(X, Y, ix, iy, reps, med[start:start + reps], out[start:start + reps], ws)
 
-        _boot.run_groups(n_iters, nx, ny, X.device, launch)
+        # (the groups are sized by the indices alone: ws_per_rep = 0)
+        _boot.replicates(nx, ny, X.device, n_iters, lambda r: _lib.mmd_workspace_bytes(nx, ny, d, r), launch, 0)
         return med.cpu().numpy(), out.cpu().numpy()

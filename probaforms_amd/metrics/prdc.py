@@ -34,8 +34,7 @@ PRDC = collections.namedtuple("PRDC", ["precision", "recall", "density", "covera
 def _check(X_real, X_fake, n_iters, nearest_k):
     """_m1d.check_args, then nearest_k: an int in 1 .. min(16, min(rows) - 1)"""
     _m1d.check_args(X_real, X_fake, n_iters)
-    if isinstance(nearest_k, bool) or not isinstance(nearest_k, (int, np.integer)) or nearest_k < 1:
-        raise ValueError("nearest_k must be a positive integer, got %r" % (nearest_k,))
+    _m1d.check_positive_int(nearest_k, "nearest_k")
     if nearest_k > _lib.KNN_MAX_K:
         raise ValueError("nearest_k is at most %d, got %d" % (_lib.KNN_MAX_K, nearest_k))
     rows = min(_boot._check_2d(A, name)[1][0] for A, name in ((X_real, "X_real"), (X_fake, "X_fake")))
@@ -45,37 +44,30 @@ def _check(X_real, X_fake, n_iters, nearest_k):
     return int(nearest_k)
 
 
-def _prepare(X_real, X_fake, n_iters, standardize):
-    Xr, Xf = _boot.prepare(X_real, X_fake, ("X_real", "X_fake"), n_iters)
-    if standardize:
-        with torch.cuda.device(Xr.device):
-            Xr, Xf = _boot.standardize(Xr, Xf)
-    return Xr, Xf
+def _counts(X_real, X_fake, n_iters, k, standardize):
+    """the checked arguments -> numpy int64 [n_iters, 4] P, Rc, Dn, Cv; n_iters = None: [1, 4] of the samples as given"""
+    n = 1 if n_iters is None else n_iters
+    Xr, Xf = _boot.prepare(X_real, X_fake, ("X_real", "X_fake"), n, standardize)
+    (nr, d), nf = Xr.shape, Xf.shape[0]
+    with torch.cuda.device(Xr.device):
+        counts = torch.empty((n, 4), dtype=torch.int64, device=Xr.device)
+        radii = []                  # a group's squared radii, real and fake
 
+        def launch(start, reps, ir, jf, ws):
+            if not radii:           # (the first group is the largest)
+                radii.extend(torch.empty(reps * rows, dtype=torch.float64, device=Xr.device) for rows in (nr, nf))
+            _lib.prdc(Xr, Xf, ir, jf, reps, k, radii[0][:reps * nr], radii[1][:reps * nf], counts[start:start + reps], ws)
 
-def _buffers(nr, nf, d, sizes, k, device):
-    """workspace and squared-radius buffers for the largest of the replicate counts `sizes`"""
-    big = max(sizes)
-    ws = torch.empty(max(_lib.prdc_workspace_bytes(nr, nf, d, r, k) for r in sizes), dtype=torch.uint8, device=device)
-    return ws, torch.empty(big * nr, dtype=torch.float64, device=device), torch.empty(big * nf, dtype=torch.float64, device=device)
+        # a replicate's radii count among the bytes that bound a group
+        _boot.replicates(nr, nf, Xr.device, n_iters, lambda r: _lib.prdc_workspace_bytes(nr, nf, d, r, k), launch,
+                         _lib.prdc_workspace_bytes(nr, nf, d, 1, k) + 8 * (nr + nf))
+        return counts.cpu().numpy()
 
 
 def _replicates(X_real, X_fake, n_iters=100, nearest_k=5, standardize=False):
     """-> numpy int64 [n_iters, 4]: the counts P, Rc, Dn, Cv of every bootstrap replicate, the draws made from numpy's
     global generator as the reference's metrics make them"""
-    k = _check(X_real, X_fake, n_iters, nearest_k)
-    Xr, Xf = _prepare(X_real, X_fake, n_iters, standardize)
-    (nr, d), nf = Xr.shape, Xf.shape[0]
-    with torch.cuda.device(Xr.device):
-        per_rep = _lib.prdc_workspace_bytes(nr, nf, d, 1, k) + 8 * (nr + nf)
-        ws, r2r, r2f = _buffers(nr, nf, d, _boot.group_sizes(n_iters, nr + nf, per_rep), k, Xr.device)
-        counts = torch.empty((n_iters, 4), dtype=torch.int64, device=Xr.device)
-
-        def launch(start, reps, ir, jf):
-            _lib.prdc(Xr, Xf, ir, jf, reps, k, r2r[:reps * nr], r2f[:reps * nf], counts[start:start + reps], ws)
-
-        _boot.run_groups(n_iters, nr, nf, Xr.device, launch, per_rep)
-        return counts.cpu().numpy()
+    return _counts(X_real, X_fake, n_iters, _check(X_real, X_fake, n_iters, nearest_k), standardize)
 
 
 # per-replicate counts of the public call, on the same draws: int64 [n_iters, 4] (P, Rc, Dn, Cv)
@@ -132,13 +124,5 @@ def prdc_full_sample(X_real, X_fake, nearest_k=5, standardize=False):
     PRDC(precision, recall, density, coverage), four numpy float64.
     '''
     k = _check(X_real, X_fake, 1, nearest_k)
-    Xr, Xf = _prepare(X_real, X_fake, 1, standardize)
-    (nr, d), nf = Xr.shape, Xf.shape[0]
-    with torch.cuda.device(Xr.device):
-        ws, r2r, r2f = _buffers(nr, nf, d, [1], k, Xr.device)
-        counts = torch.empty((1, 4), dtype=torch.int64, device=Xr.device)
-        ir = torch.arange(nr, dtype=torch.int32, device=Xr.device)
-        jf = torch.arange(nf, dtype=torch.int32, device=Xr.device)
-        _lib.prdc(Xr, Xf, ir, jf, 1, k, r2r, r2f, counts, ws)
-        M = metrics_of(counts.cpu().numpy(), nr, nf, k)
+    M = metrics_of(_counts(X_real, X_fake, None, k, standardize), len(X_real), len(X_fake), k)
     return PRDC(*[M[0, q] for q in range(4)])

@@ -40,34 +40,15 @@ Sinkhorn = collections.namedtuple("Sinkhorn", ("value", "epsilon", "drift"))
 MAX_SINKHORN = 1000000      # pfm_sinkhorn's limit on n_sinkhorn
 
 
-def _positive(v, name, none_ok=False):
-    if v is None and none_ok:
-        return
-    ok = isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
-    if not ok or not (math.isfinite(v) and v > 0 and math.isfinite(1.0 / float(v))):
-        raise ValueError("%s must be %sa positive finite number with a finite reciprocal, got %r"
-                         % (name, "None or " if none_ok else "", v))
-
-
 def _check(X_real, X_fake, n_iters, p, reg, epsilon, n_sinkhorn, standardize):
     _m1d.check_args(X_real, X_fake, n_iters)
-    if not isinstance(standardize, (bool, np.bool_)):
-        raise ValueError("standardize must be a bool, got %r" % (standardize,))
-    if isinstance(p, (bool, np.bool_)) or not isinstance(p, (int, np.integer)) or p not in (1, 2):
+    _m1d.check_bool(standardize, "standardize")
+    if not _m1d.is_int(p) or p not in (1, 2):
         raise ValueError("p must be 1 or 2, got %r" % (p,))
-    _positive(reg, "reg")
-    _positive(epsilon, "epsilon", none_ok=True)
-    ok = isinstance(n_sinkhorn, (int, np.integer)) and not isinstance(n_sinkhorn, (bool, np.bool_))
-    if not ok or not 0 <= n_sinkhorn <= MAX_SINKHORN:
+    _m1d.check_positive(reg, "reg", reciprocal=True)
+    _m1d.check_positive(epsilon, "epsilon", none_ok=True, reciprocal=True)
+    if not _m1d.is_int(n_sinkhorn) or not 0 <= n_sinkhorn <= MAX_SINKHORN:
         raise ValueError("n_sinkhorn must be an integer in 0 .. %d, got %r" % (MAX_SINKHORN, n_sinkhorn))
-
-
-def _prepare(X_real, X_fake, n_iters, standardize):
-    Xr, Xf = _boot.prepare(X_real, X_fake, ("X_real", "X_fake"), n_iters)
-    if standardize:
-        with torch.cuda.device(Xr.device):
-            Xr, Xf = _boot.standardize(Xr, Xf)
-    return Xr, Xf
 
 
 def epsilon_of(median, p, reg):
@@ -87,25 +68,29 @@ def _epsilon(Xr, Xf, p, reg, epsilon):
         return epsilon_of(_median(Xr, Xf), p, reg)
 
 
+def _run(X_real, X_fake, n_iters, p, reg, epsilon, n_sinkhorn, standardize):
+    """the checked arguments -> (numpy float64 [n_iters, 2]: value and drift of every replicate, eps); n_iters = None: [1, 2] of
+    the samples as given"""
+    n = 1 if n_iters is None else n_iters
+    Xr, Xf = _boot.prepare(X_real, X_fake, ("X_real", "X_fake"), n, standardize)
+    (nr, d), nf = Xr.shape, Xf.shape[0]
+    eps = _epsilon(Xr, Xf, p, reg, epsilon)                    # before any draw: a median of 0 raises here
+    with torch.cuda.device(Xr.device):
+        out = torch.empty((2, n), dtype=torch.float64, device=Xr.device)
+
+        def launch(start, reps, ir, jf, ws):
+            _lib.sinkhorn(Xr, Xf, ir, jf, reps, p, eps, n_sinkhorn, out[0, start:start + reps], out[1, start:start + reps],
+                          None, ws)
+
+        _boot.replicates(nr, nf, Xr.device, n_iters, lambda r: _lib.sinkhorn_workspace_bytes(nr, nf, d, r), launch)
+        return np.ascontiguousarray(out.cpu().numpy().T), eps
+
+
 def _replicates(X_real, X_fake, n_iters=100, p=2, reg=0.1, epsilon=None, n_sinkhorn=100, standardize=False):
     """-> numpy float64 [n_iters, 2]: value and drift of every bootstrap replicate, the draws made from numpy's global
     generator as the reference's metrics make them"""
     _check(X_real, X_fake, n_iters, p, reg, epsilon, n_sinkhorn, standardize)
-    Xr, Xf = _prepare(X_real, X_fake, n_iters, standardize)
-    (nr, d), nf = Xr.shape, Xf.shape[0]
-    eps = _epsilon(Xr, Xf, p, reg, epsilon)                    # before any draw: a median of 0 raises here
-    with torch.cuda.device(Xr.device):
-        per_rep = _lib.sinkhorn_workspace_bytes(nr, nf, d, 1)
-        sizes = _boot.group_sizes(n_iters, nr + nf, per_rep)
-        ws = torch.empty(max(_lib.sinkhorn_workspace_bytes(nr, nf, d, r) for r in sizes), dtype=torch.uint8, device=Xr.device)
-        out = torch.empty((2, n_iters), dtype=torch.float64, device=Xr.device)
-
-        def launch(start, reps, ir, jf):
-            _lib.sinkhorn(Xr, Xf, ir, jf, reps, p, eps, n_sinkhorn, out[0, start:start + reps], out[1, start:start + reps],
-                          None, ws)
-
-        _boot.run_groups(n_iters, nr, nf, Xr.device, launch, per_rep)
-        return np.ascontiguousarray(out.cpu().numpy().T)
+    return _run(X_real, X_fake, n_iters, p, reg, epsilon, n_sinkhorn, standardize)[0]
 
 
 # per-replicate values of the public call, on the same draws: float64 [n_iters, 2] (value, drift)
@@ -160,14 +145,5 @@ def sinkhorn_divergence_full_sample(X_real, X_fake, p=2, reg=0.1, epsilon=None, 
     last averaged iteration (the convergence diagnostic, in units of the cost); numpy float64.
     '''
     _check(X_real, X_fake, 1, p, reg, epsilon, n_sinkhorn, standardize)
-    Xr, Xf = _prepare(X_real, X_fake, 1, standardize)
-    (nr, d), nf = Xr.shape, Xf.shape[0]
-    eps = _epsilon(Xr, Xf, p, reg, epsilon)
-    with torch.cuda.device(Xr.device):
-        ws = torch.empty(_lib.sinkhorn_workspace_bytes(nr, nf, d, 1), dtype=torch.uint8, device=Xr.device)
-        out = torch.empty(2, dtype=torch.float64, device=Xr.device)
-        ir = torch.arange(nr, dtype=torch.int32, device=Xr.device)
-        jf = torch.arange(nf, dtype=torch.int32, device=Xr.device)
-        _lib.sinkhorn(Xr, Xf, ir, jf, 1, p, eps, n_sinkhorn, out[:1], out[1:], None, ws)
-        value, drift = out.cpu().numpy()
+    ((value, drift),), eps = _run(X_real, X_fake, None, p, reg, epsilon, n_sinkhorn, standardize)
     return Sinkhorn(value, eps, drift)

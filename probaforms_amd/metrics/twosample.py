@@ -52,25 +52,18 @@ def group_size(n_labellings, rows, ws_per_rep):
 
 
 def _check(X_real, X_fake, n_permutations, standardize, bandwidth=None):
-    if isinstance(n_permutations, bool) or not isinstance(n_permutations, (int, np.integer)) or n_permutations < 1:
-        raise ValueError("n_permutations must be a positive integer, got %r" % (n_permutations,))
-    if not isinstance(standardize, (bool, np.bool_)):
-        raise ValueError("standardize must be a bool, got %r" % (standardize,))
-    if bandwidth is not None:
-        ok = isinstance(bandwidth, (int, float, np.integer, np.floating)) and not isinstance(bandwidth, (bool, np.bool_))
-        if not ok or not (math.isfinite(bandwidth) and bandwidth > 0):
-            raise ValueError("bandwidth must be None or a positive finite number, got %r" % (bandwidth,))
+    _m1d.check_positive_int(n_permutations, "n_permutations")
+    _m1d.check_bool(standardize, "standardize")
+    _m1d.check_positive(bandwidth, "bandwidth", none_ok=True)
     _m1d.check_args(X_real, X_fake, 1)
 
 
 def _median(Xr, Xf):
     """the median of the pooled distance matrix of the samples as given: pfm_mmd's identity replicate"""
     (nr, d), nf = Xr.shape, Xf.shape[0]
-    ws = torch.empty(_lib.mmd_workspace_bytes(nr, nf, d, 1), dtype=torch.uint8, device=Xr.device)
     out = torch.empty(2, dtype=torch.float64, device=Xr.device)
-    ir = torch.arange(nr, dtype=torch.int32, device=Xr.device)
-    jf = torch.arange(nf, dtype=torch.int32, device=Xr.device)
-    _lib.mmd(Xr, Xf, ir, jf, 1, out[:1], out[1:], ws)
+    _boot.replicates(nr, nf, Xr.device, None, lambda r: _lib.mmd_workspace_bytes(nr, nf, d, r),
+                     lambda start, reps, ir, jf, ws: _lib.mmd(Xr, Xf, ir, jf, reps, out[:1], out[1:], ws))
     return float(out[0])
 
 
@@ -87,14 +80,36 @@ def values_of(S, nr, nf, kind):
     return (0.0 - S) / den if kind == _lib.PERM_ENERGY else (0.0 + S) / den
 
 
+def _seed():
+    """the one draw of a call from numpy's global generator"""
+    lo, hi = np.random.randint(0, 2 ** 32, size=2, dtype=np.uint64)
+    return int(lo) | int(hi) << 32
+
+
+def _labellings(seed, total, N, nr, workspace_bytes, statistic, device):
+    """The labellings of one call, group by group: the observed one (the first nr of the N pooled rows are real) in front of
+    the total - 1 drawn from `seed`.  statistic(lab, reps, start, ws) enqueues the statistic of the labellings lab
+    [reps, N] (uint8) into slots start .. start + reps - 1 of its output; ws holds workspace_bytes(reps) bytes at least."""
+    G = group_size(total, N, workspace_bytes(1))
+    ws = torch.empty(max(workspace_bytes(G), _lib.perm_labels_workspace_bytes(G, N, nr)), dtype=torch.uint8, device=device)
+    labels = torch.empty((G, N), dtype=torch.uint8, device=device)
+    for start in range(0, total, G):
+        reps = min(G, total - start)
+        lab = labels[:reps]
+        own = 1 if start == 0 else 0                                  # labelling 0 of the call is the observed one
+        if own:
+            lab[0] = (torch.arange(N, device=device) < nr).to(torch.uint8)
+        if reps > own:
+            _lib.perm_labels(seed, _lib.KEY_MASK_ALL, start + own - 1, reps - own, N, nr, lab[own:], ws)
+        statistic(lab, reps, start, ws)
+
+
 def _test(kind, X_real, X_fake, n_permutations, standardize, bandwidth):
     _check(X_real, X_fake, n_permutations, standardize, bandwidth)
-    Xr, Xf = _boot.prepare(X_real, X_fake, ("X_real", "X_fake"), 1)
+    Xr, Xf = _boot.prepare(X_real, X_fake, ("X_real", "X_fake"), 1, standardize)
     (nr, d), nf = Xr.shape, Xf.shape[0]
     N, total = nr + nf, int(n_permutations) + 1                       # the observed labelling in front of the drawn ones
     with torch.cuda.device(Xr.device):
-        if standardize:
-            Xr, Xf = _boot.standardize(Xr, Xf)
         gamma = 0.0
         if kind == _lib.PERM_GAUSS:
             sigma = float(bandwidth) if bandwidth is not None else _median(Xr, Xf)
@@ -104,25 +119,12 @@ def _test(kind, X_real, X_fake, n_permutations, standardize, bandwidth):
             gamma = 1.0 / (2 * sigma ** 2)
             if not (math.isfinite(gamma) and gamma > 0):
                 raise ValueError("gamma = 1 / (2 sigma^2) is not a positive finite number for sigma = %r" % (sigma,))
-        lo, hi = np.random.randint(0, 2 ** 32, size=2, dtype=np.uint64)
-        seed = int(lo) | int(hi) << 32
-
-        dev = Xr.device
+        seed = _seed()
         Z = torch.cat([Xr, Xf], dim=0).contiguous()
-        G = group_size(total, N, _lib.perm_form_workspace_bytes(N, d, nr, 1))
-        ws = torch.empty(max(_lib.perm_form_workspace_bytes(N, d, nr, G), _lib.perm_labels_workspace_bytes(G, N, nr)),
-                         dtype=torch.uint8, device=dev)
-        labels = torch.empty((G, N), dtype=torch.uint8, device=dev)
-        S = torch.empty(total, dtype=torch.float64, device=dev)
-        for start in range(0, total, G):
-            reps = min(G, total - start)
-            lab = labels[:reps]
-            own = 1 if start == 0 else 0                              # labelling 0 of the call is the observed one
-            if own:
-                lab[0] = (torch.arange(N, device=dev) < nr).to(torch.uint8)
-            if reps > own:
-                _lib.perm_labels(seed, _lib.KEY_MASK_ALL, start + own - 1, reps - own, N, nr, lab[own:], ws)
-            _lib.perm_form(kind, gamma, Z, nr, lab, reps, S[start:start + reps], ws)
+        S = torch.empty(total, dtype=torch.float64, device=Xr.device)
+        _labellings(seed, total, N, nr, lambda r: _lib.perm_form_workspace_bytes(N, d, nr, r),
+                    lambda lab, reps, start, ws: _lib.perm_form(kind, gamma, Z, nr, lab, reps, S[start:start + reps], ws),
+                    Xr.device)
         V = values_of(S.cpu().numpy(), nr, nf, kind)
     statistic, null = V[0], V[1:].copy()
     return TwoSampleTest(statistic, pvalue_of(statistic, null), null)
@@ -173,8 +175,7 @@ def mmd_test(X_real, X_fake, n_permutations=999, standardize=False, bandwidth=No
 
 
 def _check_k(nearest_k, N):
-    ok = isinstance(nearest_k, (int, np.integer)) and not isinstance(nearest_k, (bool, np.bool_))
-    if not ok or not 1 <= nearest_k <= min(_lib.NN_MAX_K, N - 1):
+    if not _m1d.is_int(nearest_k) or not 1 <= nearest_k <= min(_lib.NN_MAX_K, N - 1):
         raise ValueError("nearest_k must be an integer in 1 .. min(%d, n_real + n_fake - 1 = %d), got %r"
                          % (_lib.NN_MAX_K, N - 1, nearest_k))
 
@@ -191,36 +192,20 @@ def _knn(X_real, X_fake, n_permutations, nearest_k, standardize):
     nothing"""
     _check(X_real, X_fake, 1 if n_permutations is None else n_permutations, standardize)
     _check_k(nearest_k, _boot._check_2d(X_real, "X_real")[1][0] + _boot._check_2d(X_fake, "X_fake")[1][0])
-    Xr, Xf = _boot.prepare(X_real, X_fake, ("X_real", "X_fake"), 1)
+    Xr, Xf = _boot.prepare(X_real, X_fake, ("X_real", "X_fake"), 1, standardize)
     (nr, d), nf = Xr.shape, Xf.shape[0]
     N, k = nr + nf, int(nearest_k)
     total = 1 + int(n_permutations or 0)                              # the observed labelling in front of the drawn ones
     with torch.cuda.device(Xr.device):
-        if standardize:
-            Xr, Xf = _boot.standardize(Xr, Xf)
-        if total > 1:
-            lo, hi = np.random.randint(0, 2 ** 32, size=2, dtype=np.uint64)
-            seed = int(lo) | int(hi) << 32
-
+        seed = _seed() if total > 1 else None
         dev = Xr.device
         Z = torch.cat([Xr, Xf], dim=0).contiguous()
         nbr = torch.empty((N, k), dtype=torch.int32, device=dev)
         d2 = torch.empty((N, k), dtype=torch.float64, device=dev)
         _lib.nn_index(Z, k, nbr, d2, torch.empty(_lib.nn_index_workspace_bytes(N, d, k), dtype=torch.uint8, device=dev))
-        G = group_size(total, N, _lib.nn_count_workspace_bytes(N, k, 1))
-        ws = torch.empty(max(_lib.nn_count_workspace_bytes(N, k, G), _lib.perm_labels_workspace_bytes(G, N, nr)),
-                         dtype=torch.uint8, device=dev)
-        labels = torch.empty((G, N), dtype=torch.uint8, device=dev)
         counts = torch.empty((total, 2), dtype=torch.int64, device=dev)
-        for start in range(0, total, G):
-            reps = min(G, total - start)
-            lab = labels[:reps]
-            own = 1 if start == 0 else 0                              # labelling 0 of the call is the observed one
-            if own:
-                lab[0] = (torch.arange(N, device=dev) < nr).to(torch.uint8)
-            if reps > own:
-                _lib.perm_labels(seed, _lib.KEY_MASK_ALL, start + own - 1, reps - own, N, nr, lab[own:], ws)
-            _lib.nn_count(nbr, N, k, lab, reps, counts[start:start + reps], ws)
+        _labellings(seed, total, N, nr, lambda r: _lib.nn_count_workspace_bytes(N, k, r),
+                    lambda lab, reps, start, ws: _lib.nn_count(nbr, N, k, lab, reps, counts[start:start + reps], ws), dev)
         C = counts.cpu().tolist()                                     # Python ints: every ratio is rounded once
     return shares_of(C[:1], nr, nf, k)[0], np.array([(cr + cf) / (N * k) for cr, cf in C[1:]], dtype=np.float64)
 

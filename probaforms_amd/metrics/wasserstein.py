@@ -27,12 +27,6 @@ def _order(p):
     raise ValueError("p must be 1 or 2, got %r" % (p,))
 
 
-def _positive_int(v, name):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
-        raise ValueError("%s must be a positive integer, got %r" % (name, v))
-    return int(v)
-
-
 def directions(n_projections, d):
     """[n_projections, d] unit rows: normal draws from numpy's global generator, each row divided by its 2-norm"""
     th = np.random.normal(size=(n_projections, d))
@@ -40,7 +34,7 @@ def directions(n_projections, d):
 
 
 def index_groups(nr, nf, cols, n_iters, p):
-    """the number of index groups (_boot.run_groups) a call on `cols` pooled columns runs as"""
+    """the number of index groups (_boot.replicates) a call on `cols` pooled columns runs as"""
     G = _boot.group_size(n_iters, nr + nf, _lib.wasserstein1d_workspace_bytes(nr, nf, cols, 1, p))
     return -(-n_iters // G)
 
@@ -49,17 +43,13 @@ def _run(pooled, n_iters, p):
     """-> numpy [n_iters, pooled.d]: W_p^p of every bootstrap replicate of every pooled column, the draws made from
     numpy's global generator as the reference's metrics make them"""
     nr, nf, d = pooled.nr, pooled.nf, pooled.d
-    per_rep = _lib.wasserstein1d_workspace_bytes(nr, nf, d, 1, p)
-    sizes = _boot.group_sizes(n_iters, nr + nf, per_rep)
-    ws = torch.empty(max(_lib.wasserstein1d_workspace_bytes(nr, nf, d, r, p) for r in sizes), dtype=torch.uint8,
-                     device=pooled.device)
     out = torch.empty((n_iters, d), dtype=torch.float64, device=pooled.device)
 
-    def launch(start, reps, ir, jf):
+    def launch(start, reps, ir, jf, ws):
         _lib.wasserstein1d(p, pooled.cols, pooled.perm, pooled.gstart, pooled.ngroups, nr, nf, ir, jf, reps,
                            out[start:start + reps], ws)
 
-    _boot.run_groups(n_iters, nr, nf, pooled.device, launch, per_rep)
+    _boot.replicates(nr, nf, pooled.device, n_iters, lambda r: _lib.wasserstein1d_workspace_bytes(nr, nf, d, r, p), launch)
     return out.cpu().numpy()
 
 
@@ -78,12 +68,10 @@ def _replicates_1d(X_real, X_fake, n_iters=100, p=1):
 def _replicates_sliced(X_real, X_fake, n_iters=100, n_projections=64, p=2, standardize=False):
     _m1d.check_args(X_real, X_fake, n_iters)
     p = _order(p)
-    n_projections = _positive_int(n_projections, "n_projections")
-    Xr, Xf = _boot.prepare(X_real, X_fake, ("X_real", "X_fake"), n_iters)
+    n_projections = _m1d.check_positive_int(n_projections, "n_projections")
+    Xr, Xf = _boot.prepare(X_real, X_fake, ("X_real", "X_fake"), n_iters, standardize)
     with torch.cuda.device(Xr.device):
         theta = torch.from_numpy(directions(n_projections, Xr.shape[1])).to(Xr.device)
-        if standardize:
-            Xr, Xf = _boot.standardize(Xr, Xf)
         # a resample of projections is the projection of the resample: project the original rows once
         cols = torch.empty((n_projections, Xr.shape[0] + Xf.shape[0]), dtype=torch.float64, device=Xr.device)
         _lib.project(Xr, Xf, theta, cols)
