@@ -25,6 +25,11 @@ wrong (fidelity against diversity) where the distances only say how much, and th
     from probaforms_amd.metrics.energy import energy_distance, energy_distance_full_sample
     from probaforms_amd.metrics.twosample import energy_test, mmd_test, knn_test, nn_accuracy_full_sample   # permutation p-values
 
+All of these return numpy floats.  The two statistics with a closed form can also be trained on: 0-d tensors whose backward
+fills the gradient of the generated (or the real) rows, from one more sweep over the same pair tiles:
+
+    from probaforms_amd.metrics.losses import energy_loss, mmd_loss       # differentiable D^2 and biased MMD^2
+
 `__all__` and the `probaforms.metrics` alias (`probaforms_amd.install_as_probaforms()`) name only the two
 multivariate metrics, so `from probaforms.metrics import kolmogorov_smirnov_1d` raises ImportError there.
 """

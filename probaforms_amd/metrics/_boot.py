@@ -36,9 +36,10 @@ def _check_2d(A, name):
     return A, shape
 
 
-def prepare(A, B, names, n_iters, standardize=False):
+def prepare(A, B, names, n_iters, standardize=False, graph=False):
     """-> (A, B) as contiguous float64 tensors on one HIP device, standardized there if asked.  A CUDA tensor
-    stays on its device (float32 is upcast there); anything else is converted with numpy and uploaded."""
+    stays on its device (float32 is upcast there); anything else is converted with numpy and uploaded.
+    graph: tensors are not detached, so the cast, the copy and the scaler stay in their autograd graph (losses.py)."""
     from . import _m1d                    # (imports this module)
     A, sa = _check_2d(A, names[0])
     B, sb = _check_2d(B, names[1])
@@ -58,7 +59,7 @@ def prepare(A, B, names, n_iters, standardize=False):
     def dev64(t):
         if not isinstance(t, torch.Tensor):
             t = torch.from_numpy(np.ascontiguousarray(t, dtype=np.float64))
-        return t.detach().to(device=dev, dtype=torch.float64).contiguous()
+        return (t if graph else t.detach()).to(device=dev, dtype=torch.float64).contiguous()
     A, B = dev64(A), dev64(B)
     if standardize:
         with torch.cuda.device(dev):

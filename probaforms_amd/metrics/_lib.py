@@ -23,6 +23,7 @@ ENERGY_TILE = 64           # PFM_ENERGY_TILE: rows per side of a pair tile of pf
 ENERGY_REP_BLOCK = 16      # PFM_ENERGY_REP_BLOCK: replicates per count tile of pfm_energy
 PERM_ENERGY, PERM_GAUSS = 0, 1   # PFM_PERM_*: the pair value of pfm_perm_form
 KEY_MASK_ALL = 2 ** 64 - 1 # pfm_perm_labels' key_mask in use: all 64 key bits count
+PAIR_MAX_GAMMAS = 8        # PFM_PAIR_MAX_GAMMAS: Gaussians in pfm_pair_grad's kernel sum
 PFM_EINVAL, PFM_EUNSUPPORTED, PFM_EWORKSPACE = -1, -2, -3
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -58,6 +59,8 @@ _SIGNATURES = {
     "pfm_nn_index": (C.c_int, [_VP, _VP, _I64, _I64, _I64, _VP, _VP, _VP, _SZ]),
     "pfm_nn_count_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
     "pfm_nn_count": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _I64, _VP, _VP, _SZ]),
+    "pfm_pair_grad_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
+    "pfm_pair_grad": (C.c_int, [_VP, C.c_int, _VP, C.c_int, _VP, _I64, _I64, _I64, _VP, _VP, _VP, _SZ]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -305,3 +308,24 @@ def nn_count_status(nbr, n, k, labels, reps, counts, ws):
 
 def nn_count(*args):
     check(nn_count_status(*args), "pfm_nn_count")
+
+
+def pair_grad_workspace_bytes(n, d, n_first):
+    return int(lib().pfm_pair_grad_workspace_bytes(int(n), int(d), int(n_first)))
+
+
+def pair_grad_status(kind, gammas, Z, n_first, value, grad, ws):
+    """enqueue the value [1] and, unless grad is None, the row gradients [n, d] of the energy (PERM_ENERGY) or Gaussian-sum
+    (PERM_GAUSS) statistic of the pooled sample Z [n, d] on the current stream and return the status; gammas is a sequence of
+    Python floats (a host array of the C call, read before it returns)"""
+    n, d = Z.shape
+    assert value.numel() == 1 and (grad is None or tuple(grad.shape) == (n, d))
+    g = (C.c_double * max(1, len(gammas)))(*[float(v) for v in gammas])
+    return int(lib().pfm_pair_grad(torch.cuda.current_stream().cuda_stream, int(kind), C.cast(g, _VP), len(gammas),
+                                   _ptr(Z, torch.float64, "Z"), n, d, int(n_first), _ptr(value, torch.float64, "value"),
+                                   _ptr(grad, torch.float64, "grad", nullable=True), _ptr(ws, torch.uint8, "workspace"),
+                                   ws.numel()))
+
+
+def pair_grad(*args):
+    check(pair_grad_status(*args), "pfm_pair_grad")

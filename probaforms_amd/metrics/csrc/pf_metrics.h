@@ -31,9 +31,11 @@
  *                     (distance, row index), and
  *   pfm_nn_count      per labelling, how many (row, neighbour) slots carry the same label on both sides: the
  *                     nearest-neighbour two-sample test, whose neighbour table does not depend on the labelling
+ *   pfm_pair_grad     the energy distance's D^2 or the biased MMD^2 of the samples as given TOGETHER WITH its derivative by
+ *                     every row, for training on it: one more sweep over the same pair tiles, an [n, d] result
  *
  * Conventions (as include/rnvp_hip.h)
- *   - every pointer is a DEVICE pointer; sizes are plain integers;
+ *   - every pointer is a DEVICE pointer (but pfm_pair_grad's `gammas`); sizes are plain integers;
  *   - the caller owns all device memory including the workspace (no hidden hipMalloc);
  *     *_workspace_bytes() says how much a call needs;
  *   - kernels are enqueued on `stream` (a hipStream_t passed as void*) and the call
@@ -274,6 +276,35 @@ size_t pfm_perm_form_workspace_bytes(int64_t n, int64_t d, int64_t n_first, int6
  */
 int pfm_perm_form(void *stream, int kind, double gamma, const double *Z, int64_t n, int64_t d, int64_t n_first,
                   const uint8_t *labels, int64_t reps, double *S, void *workspace, size_t workspace_bytes);
+
+/* ---- differentiable two-sample losses (pf_pairgrad.hip) ------------------------------------------- */
+
+#define PFM_PAIR_MAX_GAMMAS 8   /* Gaussians in the kernel sum of PFM_PERM_GAUSS */
+
+/* bytes of workspace pfm_pair_grad needs: the workgroups' value partials and the column slices' gradient partials
+   [slices, n, d]; the number of slices depends on (n, d) only and nothing of the size of the pair matrix is kept (0: the
+   arguments are invalid or a size overflows) */
+size_t pfm_pair_grad_workspace_bytes(int64_t n, int64_t d, int64_t n_first);
+
+/*
+ * The value and the row gradients of a two-sample statistic of the pooled sample Z [n, d] (the first sample's n_first rows,
+ * then the second's n - n_first): with w[a] = +1 / n_first on a first row and -1 / (n - n_first) otherwise, and d2(a, b) the
+ * squared distance of the other entry points (fma(df, df, acc) over the features in order),
+ *   value[0]   = sum_a sum_b w[a] w[b] g(d2(a, b))                       over all ordered pairs, the diagonal included
+ *   grad[a, k] = 2 w[a] sum_b w[b] c(d2(a, b)) (Z[a, k] - Z[b, k])       = d value / d Z[a, k]
+ *   PFM_PERM_ENERGY  g = -sqrt(d2),  c = -1 / sqrt(d2), and exactly 0 where d2 == 0 (a coincident pair adds nothing)
+ *   PFM_PERM_GAUSS   g = sum_m exp(-(gammas[m] d2)),  c = -2 sum_m gammas[m] exp(-(gammas[m] d2)),  m < n_gamma
+ * so value is the energy distance's D^2 (V-statistic) or the biased MMD^2 of a sum of Gaussians.  The differences are taken
+ * feature by feature on the rows themselves: duplicated rows add exactly 0 to each other's gradient, at any offset of the data.
+ * gammas is the one HOST pointer of this header: n_gamma <= PFM_PAIR_MAX_GAMMAS positive finite values, read before the call
+ * returns and handed to the kernel by value (ignored for PFM_PERM_ENERGY, where it may be NULL).  grad [n, d] may be NULL:
+ * then only the value is formed.  Nothing is checked for NaN or infinity: they propagate.  The order of every sum depends on
+ * (n, d) only, so the outputs are bitwise the same in any call.  value [1] and every element of grad are written.
+ * PFM_EINVAL for n < 2, d < 1, n_first outside 1 .. n - 1, a bad n_gamma or gamma; PFM_EUNSUPPORTED for another kind; on any
+ * error nothing is written.
+ */
+int pfm_pair_grad(void *stream, int kind, const double *gammas, int n_gamma, const double *Z, int64_t n, int64_t d,
+                  int64_t n_first, double *value, double *grad, void *workspace, size_t workspace_bytes);
 
 /* ---- nearest-neighbour two-sample test (pf_nn.hip) ------------------------------------------------ */
 

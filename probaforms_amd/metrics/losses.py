@@ -1,0 +1,152 @@
+"""energy_loss, mmd_loss: the two closed-form two-sample statistics as differentiable losses on the GPU (kernel:
+csrc/pf_pairgrad.hip, pfm_pair_grad; host side: _boot.py, _m1d.py, twosample.py).  The reference has no such loss; the
+arguments follow energy_distance and mmd_test, real sample first.
+
+Pool Z = [X_real; X_fake] (N = nr + nf rows), w[a] = +1 / nr on a real row and -1 / nf on a fake one, d2(a, b) the squared
+distance every kernel of the library forms.  Then
+  L       = sum_ab w[a] w[b] g(d2(a, b))
+  dL/dz_a = 2 w[a] sum_b w[b] c(d2(a, b)) (z_a - z_b)
+  energy_loss   g = -sqrt(d2), c = -1 / sqrt(d2) and exactly 0 where d2 = 0: L is energy_distance_full_sample(squared=True),
+                the V-statistic D^2 (not D: sqrt has no finite derivative at 0)
+  mmd_loss      g = sum_m exp(-gamma_m d2), c = -2 sum_m gamma_m exp(-gamma_m d2), gamma_m = 1 / (2 sigma_m^2): L is the biased
+                MMD^2 of mmd_test (diagonals included); with several bandwidths the kernel is the sum of the Gaussians
+The kernel forms the value and the [N, d] row gradients in ONE sweep over the pair tiles; nothing of the size of the pair
+matrix is stored, for the forward or for the backward.  The difference z_a - z_b is taken on the rows themselves: a generated
+row that copies a real row gets a finite gradient, duplicated rows add exactly 0 to each other, and samples centred far from the
+origin lose nothing.
+
+The result is a 0-d float64 tensor on the device.  backward() fills .grad of whichever inputs require one: the node is a
+torch.autograd.Function (once differentiable) whose forward keeps the row gradients and whose backward scales and splits them.
+With no input requiring a gradient only the value is formed and the result has no grad_fn.
+
+Inputs may be numpy arrays, array-likes or torch tensors; a CUDA tensor stays on its device, slices and other views are taken
+as they are, and float32 is upcast with a torch op, so its gradient comes back as float32.  NO finiteness check of the contents
+is made (it would be a host synchronisation in every training step): NaN and infinity propagate into the value and the
+gradient.  Shape and dtype errors, a bad bandwidth and a non-bool standardize raise ValueError before anything is launched.
+With tensors on the device and a given bandwidth, forward and backward only enqueue work: nothing waits for the device.
+Importing this module needs no GPU.
+"""
+import math
+
+import numpy as np
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import _boot, _lib, _m1d
+
+NAMES = ("X_real", "X_fake")
+
+
+class PairLossFunction(torch.autograd.Function):
+    """L = sum_ab w[a] w[b] g(d2(a, b)) of the pooled rows [Xr; Xf] as one autograd node.
+
+    forward : pfm_pair_grad once: the value and, if an input requires a gradient, dL/dZ [N, d], which is kept
+    backward: dL/dZ times the incoming scalar, split into the real and the fake rows"""
+
+    @staticmethod
+    def forward(ctx, kind, gammas, Xr, Xf):
+        nr = Xr.shape[0]
+        want = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
+        Z = torch.cat([Xr.detach(), Xf.detach()], dim=0).contiguous()
+        N, d = Z.shape
+        value = torch.empty((), dtype=torch.float64, device=Z.device)
+        rows = torch.empty_like(Z) if want else None
+        ws = torch.empty(_lib.pair_grad_workspace_bytes(N, d, nr), dtype=torch.uint8, device=Z.device)
+        _lib.pair_grad(kind, gammas, Z, nr, value, rows, ws)
+        ctx.nr = nr
+        if want:
+            ctx.save_for_backward(rows)
+        return value
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gL):
+        (rows,) = ctx.saved_tensors
+        G = rows * gL
+        return (None, None, G[:ctx.nr] if ctx.needs_input_grad[2] else None,
+                G[ctx.nr:] if ctx.needs_input_grad[3] else None)
+
+
+def _gammas(bandwidth):
+    """a positive float or a sequence of 1 .. 8 of them -> the list of gamma = 1 / (2 sigma^2)"""
+    if not isinstance(bandwidth, (list, tuple)) and not (isinstance(bandwidth, np.ndarray) and bandwidth.ndim == 1):
+        sigmas = [bandwidth]
+    else:
+        sigmas = list(bandwidth)
+        if not 1 <= len(sigmas) <= _lib.PAIR_MAX_GAMMAS:
+            raise ValueError("bandwidth must be a positive finite number or a sequence of 1 to %d of them, got %d values"
+                             % (_lib.PAIR_MAX_GAMMAS, len(sigmas)))
+    out = []
+    for s in sigmas:
+        _m1d.check_positive(s, "bandwidth")
+        sq = 2 * float(s) ** 2
+        gamma = 1.0 / sq if sq > 0 else math.inf
+        if not (math.isfinite(gamma) and gamma > 0):
+            raise ValueError("gamma = 1 / (2 sigma^2) is not a positive finite number for sigma = %r" % (s,))
+        out.append(gamma)
+    return out
+
+
+def _loss(kind, X_real, X_fake, bandwidth, standardize):
+    _m1d.check_bool(standardize, "standardize")
+    gammas = [] if kind == _lib.PERM_ENERGY or bandwidth is None else _gammas(bandwidth)
+    # the scaler runs as plain torch ops: autograd carries its derivative, and the upcast's
+    Xr, Xf = _boot.prepare(X_real, X_fake, NAMES, 1, standardize, graph=True)
+    if Xr.shape[0] + Xf.shape[0] >= 2 ** 31:
+        raise ValueError("at most 2**31 - 1 pooled samples, got %d" % (Xr.shape[0] + Xf.shape[0]))
+    with torch.cuda.device(Xr.device):
+        if kind == _lib.PERM_GAUSS and bandwidth is None:
+            from . import twosample                    # (the permutation tests; imported where the median is asked for)
+            sigma = twosample._median(Xr.detach(), Xf.detach())          # one host read-back
+            if not sigma > 0:
+                raise ValueError("the median pairwise distance is 0, so gamma = 1 / (2 median^2) is infinite (too few "
+                                 "distinct rows)")
+            gammas = _gammas(sigma)
+        return PairLossFunction.apply(kind, gammas, Xr, Xf)
+
+
+def energy_loss(X_real, X_fake, standardize=False):
+    '''
+    The squared energy distance (Szekely & Rizzo) between real and fake samples as a differentiable loss.
+    D^2 = 2 E|X - Y| - E|X - X'| - E|Y - Y'| over all ordered pairs of rows (V-statistic), |.| the Euclidean norm: the value
+    of energy_distance_full_sample(squared=True).
+
+    Parameters:
+    -----------
+    X_real: array of shape [n_samples, n_features] (numpy, array-like or torch; a CUDA tensor stays on the device)
+        Real sample.
+    X_fake: array of shape [m_samples, n_features]
+        Generated sample; for training, a tensor that requires a gradient (model.nf.sample(C), a generator's output).
+    standardize: boolean
+        If True, the StandardScaler fitted on the real sample is applied to both, as torch ops (the gradient passes through
+        it). Default = False.
+
+    Return:
+    -------
+    0-d float64 tensor on the device. backward() fills the gradients of the tensor inputs that require one; a coincident
+    pair of rows adds the subgradient 0. The contents are not checked: NaN and infinity propagate.
+    '''
+    return _loss(_lib.PERM_ENERGY, X_real, X_fake, None, standardize)
+
+
+def mmd_loss(X_real, X_fake, bandwidth=None, standardize=False):
+    '''
+    The biased squared Maximum Mean Discrepancy (RBF kernel) between real and fake samples as a differentiable loss:
+    mean K_XX + mean K_YY - 2 mean K_XY, diagonals included, the statistic of mmd_test.
+
+    Parameters:
+    -----------
+    X_real, X_fake, standardize: as energy_loss.
+    bandwidth: None, float, or a sequence of 1 to 8 floats
+        sigma of the kernel exp(-d^2 / (2 sigma^2)); with a sequence the kernel is the sum of the Gaussians (the multi-scale
+        MMD loss), and the value the sum of the single-bandwidth values. Default = None: the median of the pooled distance
+        matrix of the samples as given, as mmd_test takes it. That costs one read-back to the host per call; a training
+        loop passes a number. The bandwidth is a constant: no gradient flows through it.
+
+    Return:
+    -------
+    0-d float64 tensor on the device, as energy_loss.
+
+    Raises ValueError if bandwidth is None and the median pairwise distance is 0.
+    '''
+    return _loss(_lib.PERM_GAUSS, X_real, X_fake, bandwidth, standardize)

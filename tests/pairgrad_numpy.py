@@ -1,0 +1,94 @@
+"""Float64 numpy restatement of probaforms_amd.metrics.losses (kernel: pfm_pair_grad), and the shapes its tests share.
+
+Pool Z = [X_real; X_fake], N = nr + nf, w[a] = +1 / nr on real rows and -1 / nf on fake rows (built in float64), d2(a, b) the
+sum over the features of the squared differences of the rows themselves.  Then
+  L       = sum_ab w[a] w[b] g(d2(a, b))
+  dL/dz_a = 2 w[a] sum_b w[b] c(d2(a, b)) (z_a - z_b)
+  energy: g = -sqrt(d2), c = -1 / sqrt(d2) where d2 > 0 and exactly 0 where d2 = 0
+  Gauss:  g = sum_m exp(-gamma_m d2), c = -2 sum_m gamma_m exp(-gamma_m d2), gamma_m = 1 / (2 sigma_m^2)
+The difference z_a - z_b is taken feature by feature; the expansion z_a sum_b c - sum_b c z_b is not used.
+
+Beside every sum the restatement returns the sum of the MAGNITUDES of its terms: a float64 sum of n terms taken in another order
+differs by at most about n 2^-53 of that, so the tests compare within 1e-12 of it (the project's tolerance for such sums), never
+within a fraction of the result, which cancellation can leave arbitrarily small.
+"""
+import numpy as np
+
+ENERGY, GAUSS1, GAUSS3 = "energy", "gauss1", "gauss3"
+KINDS = (ENERGY, GAUSS1, GAUSS3)
+TOL = 1e-12          # of the sum of the magnitudes of a sum's terms
+
+ROWS = ((1, 1), (2, 1), (63, 65), (64, 64), (65, 63))       # around the 64-row tile: one block, two blocks, ragged ends
+FEATURES = (1, 16, 17, 33)                                   # one chunk of 16 features, a full one, one and two spilling over
+# (nr, nf, d, flavour): flavour "plain"; "copies" = fake row 0 equals real row 0 and fake row 2 equals fake row 1;
+# "far" = centred at 1e6
+CASES = [(nr, nf, d, "plain") for nr, nf in ROWS for d in FEATURES]
+CASES += [(1200, 1000, 2, "plain"), (1200, 1000, 17, "plain")]           # several column slices, many workgroups
+CASES += [(65, 63, 17, "copies"), (130, 70, 2, "copies"), (40, 50, 5, "far"), (65, 63, 17, "far")]
+HOST_ONLY_CASES = [(1, 1, 1, "plain"), (2, 1, 3, "plain")]               # the smallest shapes there are
+
+
+def case_id(case):
+    return "%dx%d_d%d_%s" % case
+
+
+def make(case):
+    """the seeded float64 samples of a case"""
+    nr, nf, d, flavour = case
+    rng = np.random.RandomState(1000003 * nr + 1009 * nf + 7 * d + len(flavour))
+    Xr = rng.normal(size=(nr, d))
+    Xf = 0.5 + 1.25 * rng.normal(size=(nf, d))
+    if flavour == "copies":
+        Xf[0] = Xr[0]
+        Xf[2] = Xf[1]
+    elif flavour == "far":
+        Xr, Xf = Xr + 1e6, Xf + 1e6
+    return Xr, Xf
+
+
+def bandwidths(kind, d):
+    """None for the energy kind; one or three sigmas of the size of a typical distance of make()'s data"""
+    s = float(np.sqrt(2.0 * d))
+    return {ENERGY: None, GAUSS1: [s], GAUSS3: [0.5 * s, s, 2.0 * s]}[kind]
+
+
+def weights(nr, nf):
+    return np.concatenate([np.full(nr, 1.0 / nr), np.full(nf, -1.0 / nf)])
+
+
+def pair_functions(d2, sigmas):
+    """g(d2), c(d2) elementwise; sigmas None is the energy kind"""
+    if sigmas is None:
+        s = np.sqrt(d2)
+        with np.errstate(divide="ignore"):
+            c = np.where(d2 > 0, -1.0 / s, 0.0)
+        return -s, c
+    g, c = np.zeros_like(d2), np.zeros_like(d2)
+    for sigma in sigmas:
+        gamma = 1.0 / (2.0 * float(sigma) ** 2)
+        e = np.exp(-(gamma * d2))
+        g += e
+        c += gamma * e
+    return g, -2.0 * c
+
+
+def loss_and_grad(Xr, Xf, sigmas, block=128):
+    """-> (L, the sum of |terms| of L, dL/dZ [N, d], M [N, d] = 2 sum_b |w_a w_b c (z_a - z_b)[k]|), a block of rows at a time"""
+    Z = np.concatenate([np.asarray(Xr, np.float64), np.asarray(Xf, np.float64)], axis=0)
+    nr, nf = len(Xr), len(Xf)
+    w = weights(nr, nf)
+    N, d = Z.shape
+    grad, M = np.empty((N, d)), np.empty((N, d))
+    L, Lmag = 0.0, 0.0
+    for a0 in range(0, N, block):
+        diff = Z[a0:a0 + block, None, :] - Z[None, :, :]                  # [rows, N, d]
+        d2 = (diff * diff).sum(axis=2)
+        g, c = pair_functions(d2, sigmas)
+        ww = w[a0:a0 + block, None] * w[None, :]
+        terms = ww * g
+        L += terms.sum()
+        Lmag += np.abs(terms).sum()
+        t = (ww * c)[:, :, None] * diff
+        grad[a0:a0 + block] = 2.0 * t.sum(axis=1)
+        M[a0:a0 + block] = 2.0 * np.abs(t).sum(axis=1)
+    return L, Lmag, grad, M
