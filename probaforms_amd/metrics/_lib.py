@@ -61,6 +61,8 @@ _SIGNATURES = {
     "pfm_nn_count": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _I64, _VP, _VP, _SZ]),
     "pfm_pair_grad_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
     "pfm_pair_grad": (C.c_int, [_VP, C.c_int, _VP, C.c_int, _VP, _I64, _I64, _I64, _VP, _VP, _VP, _SZ]),
+    "pfm_sinkhorn_grad_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
+    "pfm_sinkhorn_grad": (C.c_int, [_VP, _VP, _I64, _I64, _I64, C.c_int, C.c_double, _I64, _VP, _VP, _VP, _VP, _VP, _SZ]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -329,3 +331,25 @@ def pair_grad_status(kind, gammas, Z, n_first, value, grad, ws):
 
 def pair_grad(*args):
     check(pair_grad_status(*args), "pfm_pair_grad")
+
+
+def sinkhorn_grad_workspace_bytes(n, d, n_first):
+    return int(lib().pfm_sinkhorn_grad_workspace_bytes(int(n), int(d), int(n_first)))
+
+
+def sinkhorn_grad_status(Z, n_first, p, eps, n_sinkhorn, value, drift, grad, potentials, ws):
+    """enqueue the debiased Sinkhorn divergence of the pooled sample Z [n, d] (n_sinkhorn + 1 steps) and, unless grad is None,
+    its row gradients [n, d] on the current stream and return the status; value / drift are float64 views of one element,
+    potentials None or a float64 view of 2 * 2 * n elements (the last step's output, then its input)"""
+    n, d = Z.shape
+    assert value.numel() == 1 == drift.numel() and (grad is None or tuple(grad.shape) == (n, d))
+    assert potentials is None or potentials.numel() == 4 * n
+    return int(lib().pfm_sinkhorn_grad(torch.cuda.current_stream().cuda_stream, _ptr(Z, torch.float64, "Z"), n, d, int(n_first),
+                                       int(p), float(eps), int(n_sinkhorn), _ptr(value, torch.float64, "value"),
+                                       _ptr(drift, torch.float64, "drift"), _ptr(grad, torch.float64, "grad", nullable=True),
+                                       _ptr(potentials, torch.float64, "potentials", nullable=True),
+                                       _ptr(ws, torch.uint8, "workspace"), ws.numel()))
+
+
+def sinkhorn_grad(*args):
+    check(sinkhorn_grad_status(*args), "pfm_sinkhorn_grad")

@@ -33,6 +33,9 @@
  *                     nearest-neighbour two-sample test, whose neighbour table does not depend on the labelling
  *   pfm_pair_grad     the energy distance's D^2 or the biased MMD^2 of the samples as given TOGETHER WITH its derivative by
  *                     every row, for training on it: one more sweep over the same pair tiles, an [n, d] result
+ *   pfm_sinkhorn_grad the debiased Sinkhorn divergence of the samples as given TOGETHER WITH its envelope-theorem derivative
+ *                     by every row: a step kernel for the one weighting whose four waves share a strip, then one sweep over
+ *                     the pair tiles with one float64 exp per pair
  *
  * Conventions (as include/rnvp_hip.h)
  *   - every pointer is a DEVICE pointer (but pfm_pair_grad's `gammas`); sizes are plain integers;
@@ -305,6 +308,40 @@ size_t pfm_pair_grad_workspace_bytes(int64_t n, int64_t d, int64_t n_first);
  */
 int pfm_pair_grad(void *stream, int kind, const double *gammas, int n_gamma, const double *Z, int64_t n, int64_t d,
                   int64_t n_first, double *value, double *grad, void *workspace, size_t workspace_bytes);
+
+/* ---- differentiable Sinkhorn divergence (pf_sinkgrad.hip) ------------------------------------------- */
+
+/* bytes of workspace pfm_sinkhorn_grad needs: three buffers of potentials and the column slices' gradient partials
+   [slices, n, d]; a function of (n, d) only, nothing of the size of the pair matrix (0: the arguments are invalid or a size
+   overflows) */
+size_t pfm_sinkhorn_grad_workspace_bytes(int64_t n, int64_t d, int64_t n_first);
+
+/*
+ * The debiased Sinkhorn divergence of the pooled sample Z [n, d] (the first sample's nr = n_first rows, then the second's
+ * nf = n - n_first) with the uniform weights a_i = 1 / nr, b_j = 1 / nf, and its row gradients.  Cost, softmin and iteration are
+ * pfm_sinkhorn's: four potentials start at 0, n_sinkhorn averaged steps from old values, one last plain step, n_sinkhorn + 1
+ * launches; the weights enter as the constants -log nr, -log nf, added once per softmin.  With `old` the potentials the last
+ * step read and `fin` the ones it wrote, slot = self where rows a and b are of one sample and cross otherwise,
+ *   value[0]   = sum_i a_i (f_i - u_i) + sum_j b_j (g_j - v_j)         of fin: pfm_sinkhorn's value of the identity replicate (not
+ *                bitwise: the sums run in another order)
+ *   drift[0]   = the largest |change| of a potential in the last averaged step (0 for n_sinkhorn = 0)
+ *   P_ab       = exp((fin_a[slot] + old_b[slot] - C_ab) / eps) / n_side(b)        (sum_b over one side = 1: no overflow)
+ *   grad[a, k] = w_a sum_b sgn_ab P_ab c_p(d2_ab) (Z[a, k] - Z[b, k]),   sgn = +1 cross, -1 self,  w_a = 1 / n_side(a),
+ *                c_2 = 2,  c_1 = 1 / sqrt(d2) and exactly 0 where d2 == 0
+ * grad differentiates every row's final softmin by that row's own coordinates only, the columns and the incoming potentials
+ * held fixed (the envelope theorem): it is the exact derivative of the value at the fixed point of the iteration, NOT the
+ * derivative of the n_sinkhorn unrolled steps; drift says how far from the fixed point the call stopped.  The differences are
+ * taken feature by feature on the rows themselves, as pfm_pair_grad takes them.
+ * grad [n, d] may be NULL: then only value and drift are formed.  potentials [2, 2, n] may be NULL: fin (cross, then self, on the
+ * pooled rows), then old.  Nothing is checked for NaN or infinity: they propagate.  The order of every sum depends on
+ * (n, n_first, d) only, so the outputs are bitwise the same in any call.  On success every element of every output given is
+ * written.
+ * PFM_EINVAL for n < 2, d < 1, n_first outside 1 .. n - 1, an eps that is not positive and finite (or whose reciprocal is not),
+ * n_sinkhorn < 0 or above 1000000; PFM_EUNSUPPORTED for a p other than 1 or 2; on any error nothing is written.
+ */
+int pfm_sinkhorn_grad(void *stream, const double *Z, int64_t n, int64_t d, int64_t n_first, int p, double eps,
+                      int64_t n_sinkhorn, double *value, double *drift, double *grad, double *potentials, void *workspace,
+                      size_t workspace_bytes);
 
 /* ---- nearest-neighbour two-sample test (pf_nn.hip) ------------------------------------------------ */
 

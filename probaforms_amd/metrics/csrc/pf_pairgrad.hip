@@ -38,27 +38,6 @@ struct Gammas {
     double g[PFM_PAIR_MAX_GAMMAS];
 };
 
-struct Slices {             // how the column tiles of a row block are shared out; a function of (n, d) only
-    int64_t nb;             // tiles per side
-    int64_t fc;             // feature chunks of the gradient
-    int64_t per;            // column tiles per slice
-    int64_t count;          // slices
-};
-
-constexpr int64_t TARGET_WORKGROUPS = 1024;    // about four per CU of the device the library is written for
-
-__host__ Slices slices_of(int64_t n, int64_t d) {
-    Slices s;
-    s.nb = tiles_per_side(n);
-    s.fc = (d + DC - 1) / DC;
-    int64_t want = (TARGET_WORKGROUPS + s.nb * s.fc - 1) / (s.nb * s.fc);
-    if (want < 1) want = 1;
-    if (want > s.nb) want = s.nb;
-    s.per = (s.nb + want - 1) / want;
-    s.count = (s.nb + s.per - 1) / s.per;
-    return s;
-}
-
 // g(d^2) and c(d^2) of one pair
 template <int KIND>
 __device__ __forceinline__ void pair_terms(double dd, const Gammas &gm, int ng, double &g, double &c) {
@@ -220,16 +199,6 @@ __global__ void __launch_bounds__(NT) k_pair_finish(const double *vpart, int64_t
         __syncthreads();
     }
     if (tid == 0) value[0] = red[0];
-}
-
-bool pair_args_ok(int64_t n, int64_t d, int64_t n_first) {
-    if (n < 2 || n > (int64_t)INT32_MAX || d < 1 || d > 65535 * (int64_t)DC) return false;      // feature chunks are grid.z
-    if (n_first < 1 || n_first >= n) return false;
-    const Slices sl = slices_of(n, d);
-    if (sl.count > 65535) return false;                                                           // slices are grid.y
-    if (d > INT64_MAX / n / sl.count / (int64_t)sizeof(double) / 2) return false;                 // the partials' bytes overflow
-    if ((n * d + NT - 1) / NT + 1 > (int64_t)INT32_MAX) return false;                             // the finish's grid.x
-    return true;
 }
 
 template <int KIND>

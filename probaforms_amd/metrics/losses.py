@@ -25,6 +25,10 @@ is made (it would be a host synchronisation in every training step): NaN and inf
 gradient.  Shape and dtype errors, a bad bandwidth and a non-bool standardize raise ValueError before anything is launched.
 With tensors on the device and a given bandwidth, forward and backward only enqueue work: nothing waits for the device.
 Importing this module needs no GPU.
+
+sinkhorn_loss is the member of the family in between, the debiased Sinkhorn divergence of sinkhorn.py with a backward()
+(kernels: csrc/pf_sinkgrad.hip, pfm_sinkhorn_grad): its gradient is the envelope-theorem gradient, exact at the fixed point of
+the iteration and NOT the derivative of the unrolled steps; see its docstring and `drift`.
 """
 import math
 
@@ -65,6 +69,39 @@ class PairLossFunction(torch.autograd.Function):
         G = rows * gL
         return (None, None, G[:ctx.nr] if ctx.needs_input_grad[2] else None,
                 G[ctx.nr:] if ctx.needs_input_grad[3] else None)
+
+
+class SinkhornLossFunction(torch.autograd.Function):
+    """The debiased Sinkhorn divergence of the pooled rows [Xr; Xf] (uniform weights) as one autograd node.
+
+    forward : pfm_sinkhorn_grad once: value, drift and, if an input requires a gradient, the envelope-theorem dS/dZ [N, d],
+              which is kept; drift is marked non-differentiable
+    backward: dS/dZ times the incoming scalar, split into the real and the fake rows"""
+
+    @staticmethod
+    def forward(ctx, p, eps, n_sinkhorn, Xr, Xf):
+        nr = Xr.shape[0]
+        want = ctx.needs_input_grad[3] or ctx.needs_input_grad[4]
+        Z = torch.cat([Xr.detach(), Xf.detach()], dim=0).contiguous()
+        N, d = Z.shape
+        value = torch.empty((), dtype=torch.float64, device=Z.device)
+        drift = torch.empty((), dtype=torch.float64, device=Z.device)
+        rows = torch.empty_like(Z) if want else None
+        ws = torch.empty(_lib.sinkhorn_grad_workspace_bytes(N, d, nr), dtype=torch.uint8, device=Z.device)
+        _lib.sinkhorn_grad(Z, nr, p, eps, n_sinkhorn, value, drift, rows, None, ws)
+        ctx.nr = nr
+        ctx.mark_non_differentiable(drift)
+        if want:
+            ctx.save_for_backward(rows)
+        return value, drift
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gS, _gdrift):
+        (rows,) = ctx.saved_tensors
+        G = rows * gS
+        return (None, None, None, G[:ctx.nr] if ctx.needs_input_grad[3] else None,
+                G[ctx.nr:] if ctx.needs_input_grad[4] else None)
 
 
 def _gammas(bandwidth):
@@ -150,3 +187,64 @@ def mmd_loss(X_real, X_fake, bandwidth=None, standardize=False):
     Raises ValueError if bandwidth is None and the median pairwise distance is 0.
     '''
     return _loss(_lib.PERM_GAUSS, X_real, X_fake, bandwidth, standardize)
+
+
+def sinkhorn_loss(X_real, X_fake, p=2, reg=0.1, epsilon=None, n_sinkhorn=100, standardize=False, return_drift=False):
+    '''
+    The debiased Sinkhorn divergence (entropic optimal transport; Genevay et al. 2018, Feydy et al. 2019) between real and fake
+    samples as a differentiable loss: the value of sinkhorn_divergence_full_sample (the same iteration with uniform weights; not
+    bitwise, the sums run in another order), the member of the family between energy_loss / mmd_loss (large eps) and W_p^p
+    (eps -> 0).
+
+    The gradient is the envelope-theorem gradient (as GeomLoss takes it): every row's final softmin is differentiated by that
+    row's own coordinates, the other rows and the incoming potentials held fixed.  That is the exact derivative of the value AT
+    THE FIXED POINT of the iteration; it is NOT the derivative of the n_sinkhorn unrolled steps.  Far from convergence the two
+    differ (by 10 - 30 % of the largest element at drift = 0.1 in units of the cost): ask for return_drift=True and watch drift,
+    the largest change of a potential in the last averaged step.  Nothing of the size of the pair matrix is stored, for the
+    forward or for the backward, and no graph of the steps is kept.
+
+    Parameters:
+    -----------
+    X_real, X_fake, standardize: as energy_loss.
+    p: int
+        The cost is the Euclidean distance to the power p, 1 or 2. Default = 2. For p = 1 a coincident pair of rows adds the
+        subgradient 0.
+    reg: float
+        eps = reg * median^p, median being the median pairwise distance of the pooled samples as given (after standardize).
+        Default = 0.1.
+    epsilon: None or float
+        The entropic regularisation eps itself, in units of the cost; reg is then not used. Default = None: eps from the median,
+        which costs one read-back to the host per call; a training loop passes a number. eps is a constant: no gradient flows
+        through it.
+    n_sinkhorn: int
+        The number of averaged iterations before the final one, 0 .. 1000000. Default = 100.
+    return_drift: boolean
+        If True, (loss, drift) is returned, drift a 0-d float64 tensor on the device without a grad_fn (reading it waits for
+        the device; the call does not). Default = False.
+
+    Return:
+    -------
+    0-d float64 tensor on the device, as energy_loss; with no input requiring a gradient only the value is formed. The contents
+    are not checked: NaN and infinity propagate.
+
+    Raises ValueError if epsilon is None and the median pairwise distance is 0.
+    '''
+    from . import sinkhorn as _sk                      # (the metric: its limits and eps = reg * median^p; imports twosample)
+    _m1d.check_bool(standardize, "standardize")
+    _m1d.check_bool(return_drift, "return_drift")
+    if not _m1d.is_int(p) or p not in (1, 2):
+        raise ValueError("p must be 1 or 2, got %r" % (p,))
+    _m1d.check_positive(reg, "reg", reciprocal=True)
+    _m1d.check_positive(epsilon, "epsilon", none_ok=True, reciprocal=True)
+    if not _m1d.is_int(n_sinkhorn) or not 0 <= n_sinkhorn <= _sk.MAX_SINKHORN:
+        raise ValueError("n_sinkhorn must be an integer in 0 .. %d, got %r" % (_sk.MAX_SINKHORN, n_sinkhorn))
+    Xr, Xf = _boot.prepare(X_real, X_fake, NAMES, 1, standardize, graph=True)
+    if Xr.shape[0] + Xf.shape[0] >= 2 ** 31:
+        raise ValueError("at most 2**31 - 1 pooled samples, got %d" % (Xr.shape[0] + Xf.shape[0]))
+    with torch.cuda.device(Xr.device):
+        if epsilon is None:
+            eps = float(_sk.epsilon_of(_sk._median(Xr.detach(), Xf.detach()), p, reg))     # one host read-back
+        else:
+            eps = float(epsilon)
+        value, drift = SinkhornLossFunction.apply(int(p), eps, int(n_sinkhorn), Xr, Xf)
+    return (value, drift) if return_drift else value

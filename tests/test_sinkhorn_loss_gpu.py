@@ -1,0 +1,381 @@
+"""probaforms_amd.metrics.losses.sinkhorn_loss on the GPU (pfm_sinkhorn_grad in libpf_metrics.so) against the float64
+restatement (tests/sinkhorn_grad_numpy.py), sinkhorn_divergence_full_sample, torch's gradcheck, and through the flow's
+differentiable sampling.
+
+Tolerances.  Value and drift: 1e-11 cmax, cmax the largest cost between two pooled rows, the bound tests/test_sinkhorn_gpu.py
+holds the metric to.  A gradient element: (1e-12 + 2e-11 cmax / eps) M, M[a, k] the sum of the magnitudes of the element's own
+terms from the restatement: 1e-12 is the project's tolerance for a float64 sum taken in another order, and the potentials' 1e-11
+cmax (the row's fin and the column's old: twice) carried through the exponent changes every term by at most 2e-11 cmax / eps of
+itself.  The largest deviations seen are printed by test_zz_largest_deviation.
+
+Shapes: tests/pairgrad_numpy.py ROWS x FEATURES (two and three pooled rows, the 64-row tile exactly and one row either side; one
+feature chunk exactly, one and two spilling over), (1200, 1000, 2) (several column slices, the four-feature sweep) and
+(300, 200, 17) (two feature chunks), each with p = 1 and 2 at 7 steps; 0, 1, 2 and 7 steps (both ping-pong parities, the
+step-free edge) and reg = 0.1 and 1 around (65, 63, 17); copied and duplicated rows and data centred at 1e6.  eps is given as
+reg * median^p, the median taken in numpy.
+"""
+import functools
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import hygiene  # noqa: E402
+import native_libs  # noqa: E402
+import pairgrad_numpy as pg  # noqa: E402
+import sinkhorn_grad_numpy as sg  # noqa: E402
+import sinkhorn_numpy as sn  # noqa: E402
+from probaforms_amd.metrics import _boot, _lib, losses, sinkhorn as sk  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+native_libs.ensure_built(_lib)
+
+ATOL = 1e-11                    # of cmax: value, drift, potentials
+MIDDLE = (65, 63, 17, "plain")
+SHAPES = [(nr, nf, d, "plain") for nr, nf in pg.ROWS for d in pg.FEATURES] + [(1200, 1000, 2, "plain"), (300, 200, 17, "plain")]
+FLAVOURS = [(65, 63, 17, "copies"), (130, 70, 2, "copies"), (40, 50, 5, "far"), (65, 63, 17, "far")]
+# (case, p, n_sinkhorn, reg)
+CONFIGS = [(c, p, 7, 0.1) for c in SHAPES for p in (1, 2)]
+CONFIGS += [(MIDDLE, p, n, reg) for p in (1, 2) for n in (0, 1, 2, 7) for reg in (0.1, 1.0)]
+CONFIGS += [(c, p, 7, reg) for c in FLAVOURS for p in (1, 2) for reg in (0.1, 1.0)]
+CONFIGS = sorted(set(CONFIGS))
+WORST = {"value": 0.0, "grad": 0.0}
+
+
+def config_id(cfg):
+    return "%s_p%d_n%d_reg%g" % ((pg.case_id(cfg[0]),) + cfg[1:])
+
+
+def dev(A, grad=False, dtype=torch.float64):
+    return torch.from_numpy(np.array(A)).to(device="cuda", dtype=dtype).requires_grad_(grad)
+
+
+@functools.lru_cache(maxsize=None)
+def reference(cfg):
+    """(Xr, Xf, eps, cmax, restatement dict) of a configuration: computed once, shared, never written to"""
+    case, p, n, reg = cfg
+    Xr, Xf = pg.make(case)
+    eps = float(reg * sn.median(Xr, Xf) ** p)
+    o = sg.value_drift_grad(Xr, Xf, p, eps, n)
+    for a in (Xr, Xf) + tuple(v for v in o.values() if isinstance(v, np.ndarray)):
+        a.setflags(write=False)
+    return Xr, Xf, eps, sn.cmax(Xr, Xf, p), o
+
+
+def grad_tol(cm, eps):
+    return 1e-12 + 2e-11 * cm / eps
+
+
+def assert_close(S, drift, grad, cfg, what):
+    _, _, eps, cm, want = reference(cfg)
+    verr = max(abs(float(S.detach()) - want["value"]), abs(float(drift) - want["drift"])) / cm
+    gerr = np.abs(grad - want["grad"])
+    rel = float((gerr / np.where(want["M"] > 0, want["M"], 1.0)).max()) / grad_tol(cm, eps)
+    WORST["value"], WORST["grad"] = max(WORST["value"], verr), max(WORST["grad"], rel)
+    print("%s: value / drift off by %.3g cmax, gradient by at most %.3g of its bound" % (what, verr, rel))
+    assert np.isfinite(grad).all(), what
+    assert verr <= ATOL, what
+    assert (gerr <= grad_tol(cm, eps) * want["M"]).all(), what
+
+
+# ---- value, drift and gradient against the restatement and the metric -------------------------------------
+
+@pytest.mark.parametrize("cfg", CONFIGS, ids=config_id)
+def test_value_drift_and_gradient_equal_the_restatement(cfg):
+    case, p, n, reg = cfg
+    Xr, Xf, eps, cm, want = reference(cfg)
+    A, B = dev(Xr, True), dev(Xf, True)
+    S, drift = losses.sinkhorn_loss(A, B, p=p, epsilon=eps, n_sinkhorn=n, return_drift=True)
+    assert S.shape == () and S.dtype == torch.float64 and S.is_cuda and S.grad_fn is not None
+    assert drift.shape == () and drift.dtype == torch.float64 and drift.is_cuda and drift.grad_fn is None
+    assert not drift.requires_grad
+    S.backward()
+    grad = torch.cat([A.grad, B.grad]).cpu().numpy()
+    assert_close(S, drift, grad, cfg, config_id(cfg))
+    if n == 0:
+        assert float(drift) == 0.0
+    if case[3] == "copies":           # duplicated fake rows see every row alike
+        assert hygiene.same_bits(B.grad[1], B.grad[2])
+    metric = sk.sinkhorn_divergence_full_sample(Xr, Xf, p=p, epsilon=eps, n_sinkhorn=n)
+    assert abs(float(S.detach()) - metric.value) <= ATOL * cm and abs(float(drift) - metric.drift) <= ATOL * cm
+
+
+def test_potentials_of_the_raw_call_equal_the_restatement():
+    for cfg in ((MIDDLE, 1, 2, 0.1), (MIDDLE, 2, 7, 1.0), ((1200, 1000, 2, "plain"), 2, 7, 0.1)):
+        Xr, Xf, eps, cm, want = reference(cfg)
+        Z = dev(np.concatenate([Xr, Xf]))
+        N, d = Z.shape
+        out = [torch.empty(s, dtype=torch.float64, device="cuda") for s in (1, 1, (N, d), (2, 2, N))]
+        ws = hygiene.workspace(_lib.sinkhorn_grad_workspace_bytes(N, d, len(Xr)), "ones")
+        assert _lib.sinkhorn_grad_status(Z, len(Xr), cfg[1], eps, cfg[2], out[0], out[1], out[2], out[3], ws) == 0
+        pots = out[3].cpu().numpy()
+        assert np.abs(pots[0] - want["fin"]).max() <= ATOL * cm and np.abs(pots[1] - want["old"]).max() <= ATOL * cm
+
+
+def test_epsilon_from_the_median():
+    Xr, Xf = pg.make(MIDDLE)
+    for p, reg in ((1, 0.1), (2, 1.0)):
+        eps = reg * sn.median(Xr, Xf) ** p
+        got = losses.sinkhorn_loss(Xr, Xf, p=p, reg=reg, n_sinkhorn=7)
+        want = losses.sinkhorn_loss(Xr, Xf, p=p, epsilon=eps, n_sinkhorn=7)
+        metric = sk.sinkhorn_divergence_full_sample(Xr, Xf, p=p, reg=reg, n_sinkhorn=7)
+        assert abs(metric.epsilon - eps) <= 1e-13 * eps
+        assert abs(float(got) - float(want)) <= ATOL * sn.cmax(Xr, Xf, p)
+    with pytest.raises(ValueError, match="median pairwise distance is 0"):
+        losses.sinkhorn_loss(np.ones((6, 2)), np.ones((5, 2)))
+
+
+# ---- gradcheck and translation invariance at converged configurations ---------------------------------------
+
+@pytest.mark.parametrize("case", sg.CONVERGED, ids=str)
+def test_gradcheck_on_the_public_function(case):
+    nr, nf, d, eps, p, n = case
+    Xr, Xf = sg.converged_data(nr, nf, d)
+    assert torch.autograd.gradcheck(lambda a, b: losses.sinkhorn_loss(a, b, p=p, epsilon=eps, n_sinkhorn=n),
+                                    (dev(Xr, True), dev(Xf, True)))
+
+
+@pytest.mark.parametrize("case", sg.CONVERGED, ids=str)
+def test_converged_gradient_sums_to_zero_over_the_rows(case):
+    nr, nf, d, eps, p, n = case
+    Xr, Xf = sg.converged_data(nr, nf, d)
+    want = sg.value_drift_grad(Xr, Xf, p, eps, n)
+    A, B = dev(Xr, True), dev(Xf, True)
+    S, drift = losses.sinkhorn_loss(A, B, p=p, epsilon=eps, n_sinkhorn=n, return_drift=True)
+    S.backward()
+    grad = torch.cat([A.grad, B.grad]).cpu().numpy()
+    cm = sn.cmax(Xr, Xf, p)
+    bound = grad_tol(cm, eps) * want["M"]
+    print("%s: drift %.3g, columns sum to %s, bound %s" % (case, float(drift), grad.sum(axis=0), bound.sum(axis=0)))
+    assert float(drift) <= 1e-13 + ATOL * cm
+    assert (np.abs(grad - want["grad"]) <= bound).all()
+    assert (np.abs(grad.sum(axis=0)) <= bound.sum(axis=0)).all()
+
+
+# ---- inputs and routing ---------------------------------------------------------------------------------------
+
+KW = dict(p=2, n_sinkhorn=7)
+
+
+def middle(p=2):
+    cfg = (MIDDLE, p, 7, 0.1)
+    return (cfg,) + reference(cfg)
+
+
+def test_gradient_goes_to_the_inputs_that_ask(monkeypatch):
+    cfg, Xr, Xf, eps, cm, want = middle()
+    both = [dev(Xr, True), dev(Xf, True)]
+    losses.sinkhorn_loss(both[0], both[1], epsilon=eps, **KW).backward()
+    A, B = dev(Xr), dev(Xf, True)
+    losses.sinkhorn_loss(A, B, epsilon=eps, **KW).backward()
+    assert A.grad is None and hygiene.same_bits(B.grad, both[1].grad)
+    A, B = dev(Xr, True), dev(Xf)
+    losses.sinkhorn_loss(A, B, epsilon=eps, **KW).backward()
+    assert B.grad is None and hygiene.same_bits(A.grad, both[0].grad)
+    # the incoming scalar
+    A, B = dev(Xr, True), dev(Xf, True)
+    (3 * losses.sinkhorn_loss(A, B, epsilon=eps, **KW)).backward()
+    assert torch.equal(A.grad, 3 * both[0].grad) and torch.equal(B.grad, 3 * both[1].grad)
+    # neither: the value alone, no node, and the gradient buffer is never allocated; numpy inputs as well
+    seen = []
+    status = _lib.sinkhorn_grad_status
+
+    def spy(Z, n_first, p, e, n, value, drift, grad, potentials, ws):
+        seen.append(grad)
+        return status(Z, n_first, p, e, n, value, drift, grad, potentials, ws)
+    monkeypatch.setattr(_lib, "sinkhorn_grad_status", spy)
+    for a, b in ((dev(Xr), dev(Xf)), (Xr, Xf), (Xr.tolist(), dev(Xf))):
+        V, drift = losses.sinkhorn_loss(a, b, epsilon=eps, return_drift=True, **KW)
+        assert V.grad_fn is None and not V.requires_grad and V.is_cuda and V.dtype == torch.float64
+        assert drift.grad_fn is None and not drift.requires_grad
+        assert abs(float(V) - want["value"]) <= ATOL * cm
+    assert len(seen) == 3 and all(g is None for g in seen)
+
+
+def test_float32_inputs_get_float32_gradients():
+    cfg, Xr, Xf, eps, cm, want = middle()
+    A, B = dev(Xr, True, torch.float32), dev(Xf, True, torch.float32)
+    S = losses.sinkhorn_loss(A, B, epsilon=eps, **KW)
+    assert S.dtype == torch.float64
+    S.backward()
+    assert A.grad.dtype == torch.float32 == B.grad.dtype and A.grad.shape == A.shape and B.grad.shape == B.shape
+    A64, B64 = A.detach().double().requires_grad_(True), B.detach().double().requires_grad_(True)
+    S64 = losses.sinkhorn_loss(A64, B64, epsilon=eps, **KW)
+    S64.backward()
+    assert hygiene.same_bits(S.reshape(1), S64.reshape(1))                                    # the upcast is exact
+    assert torch.equal(A.grad, A64.grad.float()) and torch.equal(B.grad, B64.grad.float())     # one rounding, at the end
+
+
+def test_views_give_the_gradient_of_the_contiguous_copy():
+    cfg, Xr, Xf, eps, cm, want = middle()
+    A, B = dev(Xr), dev(Xf, True)
+    losses.sinkhorn_loss(A, B, epsilon=eps, **KW).backward()
+    wide = torch.full((63, 17 + 5), 7.0, dtype=torch.float64, device="cuda")
+    wide[:, 2:19] = B.detach()
+    wide.requires_grad_(True)
+    losses.sinkhorn_loss(A, wide[:, 2:19], epsilon=eps, **KW).backward()
+    assert hygiene.same_bits(wide.grad[:, 2:19], B.grad)
+    assert not wide.grad[:, :2].any() and not wide.grad[:, 19:].any()
+    T = B.detach().t().contiguous().requires_grad_(True)               # [d, nf]: the sample is its transposed view
+    losses.sinkhorn_loss(A, T.t(), epsilon=eps, **KW).backward()
+    assert hygiene.same_bits(T.grad.t(), B.grad)
+    every = B.detach().repeat_interleave(2, dim=0).requires_grad_(True)       # every second row
+    losses.sinkhorn_loss(A[::1], every[::2], epsilon=eps, **KW).backward()
+    assert hygiene.same_bits(every.grad[::2], B.grad) and not every.grad[1::2].any()
+
+
+def test_standardize_equals_the_scaler_composed_by_hand():
+    Xr, Xf = pg.make((40, 50, 5, "plain"))
+    scale, shift = np.array([1.0, 10.0, 0.1, 3.0, 1.0]), np.array([0.0, 5.0, -2.0, 100.0, 1.0])
+    Xr, Xf = Xr * scale + shift, Xf * scale + shift
+    A, B = dev(Xr, True), dev(Xf, True)
+    S = losses.sinkhorn_loss(A, B, epsilon=0.8, standardize=True, **KW)
+    S.backward()
+    A2, B2 = dev(Xr, True), dev(Xf, True)
+    As, Bs = _boot.standardize(A2, B2)
+    S2 = losses.sinkhorn_loss(As, Bs, epsilon=0.8, **KW)
+    S2.backward()
+    # the same torch ops feed the same kernel: the same value bits; the scaler's backward sums in torch's own order
+    assert hygiene.same_bits(S.reshape(1), S2.reshape(1))
+    for g, g2 in ((A.grad, A2.grad), (B.grad, B2.grad)):
+        assert float((g - g2).abs().max()) <= 1e-13 * float(g2.abs().max())
+    # and the standardized samples' value is the restatement's
+    Zs = torch.cat([As, Bs]).detach().cpu().numpy()
+    want = sg.value_drift_grad(Zs[:40], Zs[40:], 2, 0.8, 7)
+    assert abs(float(S) - want["value"]) <= ATOL * sn.cmax(Zs[:40], Zs[40:], 2)
+    assert bool(A.grad.ne(0).any()) and bool(torch.isfinite(A.grad).all())
+
+
+# ---- reproducibility and workspace hygiene -----------------------------------------------------------------
+
+def test_two_calls_give_identical_bytes():
+    cfg = ((1200, 1000, 2, "plain"), 2, 7, 0.1)
+    Xr, Xf, eps = reference(cfg)[:3]
+    outs = []
+    for _ in range(2):
+        A, B = dev(Xr, True), dev(Xf, True)
+        S, drift = losses.sinkhorn_loss(A, B, epsilon=eps, return_drift=True, **KW)
+        S.backward()
+        outs.append((S.detach().reshape(1), drift.reshape(1), A.grad, B.grad))
+        torch.empty(1 << 22, device="cuda").fill_(float("nan"))          # the allocator hands other memory to the next call
+    for a, b in zip(*outs):
+        assert hygiene.same_bits(a, b)
+
+
+@pytest.mark.parametrize("p", (1, 2))
+@pytest.mark.parametrize("case", [(65, 63, 17, "plain"), (1200, 1000, 2, "plain"), (2, 1, 33, "plain")], ids=pg.case_id)
+def test_outputs_do_not_depend_on_the_workspace(case, p):
+    Xr, Xf, eps = reference((case, p, 7, 0.1))[:3]
+    Z = dev(np.concatenate([Xr, Xf]))
+    nr, (N, d) = len(Xr), Z.shape
+    nbytes = _lib.sinkhorn_grad_workspace_bytes(N, d, nr)
+
+    def outputs(grad=True):
+        o = {"value": torch.empty(1, dtype=torch.float64, device="cuda"), "drift": torch.empty(1, dtype=torch.float64, device="cuda"),
+             "potentials": torch.empty((2, 2, N), dtype=torch.float64, device="cuda")}
+        if grad:
+            o["grad"] = torch.empty_like(Z)
+        hygiene.poison_outputs(*o.values())
+        return o
+
+    outs = {}
+    for pattern in hygiene.PATTERNS:
+        ws = hygiene.workspace(nbytes, pattern)
+        if pattern == "replay":                                           # as another call left it: other data, other split
+            o = outputs()
+            assert _lib.sinkhorn_grad_status((Z * 3.0 + 1.0).contiguous(), max(1, nr // 2), 3 - p, 2 * eps, 4, o["value"],
+                                             o["drift"], o["grad"], o["potentials"], ws) == 0
+        for steps, tag in ((7, ""), (2, "_even")):                        # both parities of the ping-pong
+            o = outputs()
+            assert _lib.sinkhorn_grad_status(Z, nr, p, eps, steps, o["value"], o["drift"], o["grad"], o["potentials"], ws) == 0
+            v = outputs(grad=False)
+            assert _lib.sinkhorn_grad_status(Z, nr, p, eps, steps, v["value"], v["drift"], None, v["potentials"],
+                                             hygiene.workspace(nbytes, pattern)) == 0
+            torch.cuda.synchronize()
+            got = {k + tag: t for k, t in o.items()}
+            got.update({"only_" + k + tag: t for k, t in v.items()})
+            outs.setdefault(pattern, {}).update(got)
+            for k in ("value", "drift", "potentials"):                    # the value alone is formed alike
+                assert hygiene.same_bits(o[k], v[k])
+        hygiene.assert_all_written(outs[pattern], "pfm_sinkhorn_grad %s %s" % (pg.case_id(case), pattern))
+    hygiene.assert_pattern_independent(outs, "pfm_sinkhorn_grad %s" % pg.case_id(case))
+
+
+# ---- no host synchronisation -------------------------------------------------------------------------------
+
+def test_forward_and_backward_never_wait_for_the_device():
+    cfg, Xr, Xf, eps, cm, want = middle()
+    A = dev(Xr)
+    W = dev(np.concatenate([Xf, Xf], axis=1), True)
+    losses.sinkhorn_loss(A, W[:, :17], epsilon=eps, **KW).backward()        # warm-up: library, code objects, allocator
+    W.grad = None
+    torch.cuda.synchronize()
+    mode = torch.cuda.get_sync_debug_mode()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        S, drift = losses.sinkhorn_loss(A, W[:, :17], epsilon=eps, return_drift=True, **KW)
+        (2 * S).backward()
+        V = losses.sinkhorn_loss(A, W[:, :17].detach(), epsilon=eps, standardize=True, **KW)
+    finally:
+        torch.cuda.set_sync_debug_mode(mode)
+    assert bool(torch.isfinite(W.grad).all()) and bool(W.grad[:, :17].ne(0).any())
+    assert float(drift) == want["drift"] or abs(float(drift) - want["drift"]) <= ATOL * cm
+    assert bool(torch.isfinite(V))
+
+
+# ---- copies, NaN -------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("p", (1, 2))
+def test_copied_and_duplicated_rows_get_finite_gradients(p):
+    Xr, Xf = pg.make((65, 63, 17, "copies"))
+    assert (Xf[0] == Xr[0]).all() and (Xf[2] == Xf[1]).all()
+    B = dev(Xf, True)
+    S = losses.sinkhorn_loss(dev(Xr), B, p=p, epsilon=0.1 * sn.median(Xr, Xf) ** p, n_sinkhorn=7)
+    S.backward()
+    assert bool(torch.isfinite(S)) and bool(torch.isfinite(B.grad).all())
+    assert bool(B.grad[0].ne(0).any()) and hygiene.same_bits(B.grad[1], B.grad[2])
+
+
+def test_nan_propagates_and_is_not_checked():
+    Xr, Xf = pg.make(MIDDLE)
+    Xf = Xf.copy()
+    Xf[3, 2] = np.nan
+    for p in (1, 2):
+        B = dev(Xf, True)
+        S = losses.sinkhorn_loss(dev(Xr), B, p=p, epsilon=1.0, n_sinkhorn=3)
+        S.backward()
+        assert bool(torch.isnan(S))
+
+
+# ---- through the flow seam ---------------------------------------------------------------------------------
+
+def test_sinkhorn_loss_reaches_a_flows_parameters_through_its_sampler():
+    from probaforms_amd.models import RealNVP
+    rng = np.random.RandomState(5)
+    n = 300
+    C0 = rng.uniform(-1, 1, size=(n, 1)).astype(np.float32)
+    X0 = (np.concatenate([np.sin(3 * C0), np.cos(3 * C0)], axis=1) + 0.1 * rng.normal(size=(n, 2))).astype(np.float32)
+    torch.manual_seed(7)
+    model = RealNVP(n_layers=3, hidden=(8,), n_epochs=1, batch_size=100)
+    model.fit(X0, C0)
+    for q in model.nf.parameters():
+        q.grad = None
+    C = torch.from_numpy(C0).cuda()
+    X = torch.from_numpy(X0).cuda()
+    S = losses.sinkhorn_loss(torch.cat([X, C], 1), torch.cat([model.nf.sample(C), C], 1), p=2, epsilon=0.05, n_sinkhorn=20)
+    assert S.grad_fn is not None and bool(torch.isfinite(S))
+    S.backward()
+    grads = [q.grad for q in model.nf.parameters()]
+    assert all(g is not None and bool(torch.isfinite(g).all()) for g in grads)
+    assert any(bool(g.ne(0).any()) for g in grads)
+
+
+def test_zz_largest_deviation():
+    print("largest deviation seen: value / drift %.3g cmax (bound %.3g), gradient %.3g of its bound"
+          % (WORST["value"], ATOL, WORST["grad"]))
