@@ -24,6 +24,7 @@ ENERGY_REP_BLOCK = 16      # PFM_ENERGY_REP_BLOCK: replicates per count tile of 
 PERM_ENERGY, PERM_GAUSS = 0, 1   # PFM_PERM_*: the pair value of pfm_perm_form
 KEY_MASK_ALL = 2 ** 64 - 1 # pfm_perm_labels' key_mask in use: all 64 key bits count
 PAIR_MAX_GAMMAS = 8        # PFM_PAIR_MAX_GAMMAS: Gaussians in pfm_pair_grad's kernel sum
+SLICE_LDS_ROWS = 13312     # PFM_SLICE_LDS_ROWS: rows per sample pfm_slice_grad sorts itself, in LDS
 PFM_EINVAL, PFM_EUNSUPPORTED, PFM_EWORKSPACE = -1, -2, -3
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -63,6 +64,8 @@ _SIGNATURES = {
     "pfm_pair_grad": (C.c_int, [_VP, C.c_int, _VP, C.c_int, _VP, _I64, _I64, _I64, _VP, _VP, _VP, _SZ]),
     "pfm_sinkhorn_grad_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
     "pfm_sinkhorn_grad": (C.c_int, [_VP, _VP, _I64, _I64, _I64, C.c_int, C.c_double, _I64, _VP, _VP, _VP, _VP, _VP, _SZ]),
+    "pfm_slice_grad_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64]),
+    "pfm_slice_grad": (C.c_int, [_VP, C.c_int, _VP, _I64, _I64, _I64, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _SZ]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -353,3 +356,30 @@ def sinkhorn_grad_status(Z, n_first, p, eps, n_sinkhorn, value, drift, grad, pot
 
 def sinkhorn_grad(*args):
     check(sinkhorn_grad_status(*args), "pfm_sinkhorn_grad")
+
+
+def slice_grad_workspace_bytes(n, d, n_first, n_proj):
+    return int(lib().pfm_slice_grad_workspace_bytes(int(n), int(d), int(n_first), int(n_proj)))
+
+
+def slice_grad_status(p, Z, n_first, theta, n_proj, perm_in, value, rows, cols_out, perm_out, ws):
+    """enqueue the sliced Wasserstein value [1] (no p-th root) of the pooled sample Z [n, d] over the directions theta [n_proj, d]
+    (None: the coordinate axes, n_proj = d) and, unless rows is None, its row gradients [n, d] on the current stream and return the
+    status; perm_in None (the kernel sorts, at most SLICE_LDS_ROWS rows per sample) or int32 [n_proj, n], each direction's real rows
+    in order, then its fake rows; cols_out (float64) / perm_out (int32) None or [n_proj, n]: the projections and the order used"""
+    n, d = Z.shape
+    assert value.numel() == 1 and (rows is None or tuple(rows.shape) == (n, d))
+    assert theta is None or tuple(theta.shape) == (n_proj, d)
+    for t in (perm_in, cols_out, perm_out):
+        assert t is None or tuple(t.shape) == (n_proj, n)
+    return int(lib().pfm_slice_grad(torch.cuda.current_stream().cuda_stream, int(p), _ptr(Z, torch.float64, "Z"), n, d,
+                                    int(n_first), _ptr(theta, torch.float64, "theta", nullable=True), int(n_proj),
+                                    _ptr(perm_in, torch.int32, "perm_in", nullable=True), _ptr(value, torch.float64, "value"),
+                                    _ptr(rows, torch.float64, "rows", nullable=True),
+                                    _ptr(cols_out, torch.float64, "cols_out", nullable=True),
+                                    _ptr(perm_out, torch.int32, "perm_out", nullable=True), _ptr(ws, torch.uint8, "workspace"),
+                                    ws.numel()))
+
+
+def slice_grad(*args):
+    check(slice_grad_status(*args), "pfm_slice_grad")

@@ -36,6 +36,9 @@
  *   pfm_sinkhorn_grad the debiased Sinkhorn divergence of the samples as given TOGETHER WITH its envelope-theorem derivative
  *                     by every row: a step kernel for the one weighting whose four waves share a strip, then one sweep over
  *                     the pair tiles with one float64 exp per pair
+ *   pfm_slice_grad    the sliced Wasserstein distance of the samples as given TOGETHER WITH its derivative by every row: per
+ *                     direction a (value, row) sort of each sample in LDS, the quantile coupling of the two sorted samples and
+ *                     its gradient, O(P n log n) where the three above walk n^2 pairs
  *
  * Conventions (as include/rnvp_hip.h)
  *   - every pointer is a DEVICE pointer (but pfm_pair_grad's `gammas`); sizes are plain integers;
@@ -66,7 +69,8 @@ extern "C" {
 #define PFM_EINVAL       (-1)   /* NULL pointer, non-positive size, index range       */
 #define PFM_EUNSUPPORTED (-2)   /* d too large for the moments kernels' LDS row tile;
                                    a Wasserstein order or Sinkhorn cost power p other than 1 or 2;
-                                   nearest_k above PFM_KNN_MAX_K; k above PFM_NN_MAX_K    */
+                                   nearest_k above PFM_KNN_MAX_K; k above PFM_NN_MAX_K;
+                                   a sample above PFM_SLICE_LDS_ROWS without perm_in      */
 #define PFM_EWORKSPACE   (-3)   /* workspace smaller than *_workspace_bytes() says      */
 
 #define PFM_VERSION 101         /* pfm_version(): bumped whenever an argument list changes */
@@ -342,6 +346,46 @@ size_t pfm_sinkhorn_grad_workspace_bytes(int64_t n, int64_t d, int64_t n_first);
 int pfm_sinkhorn_grad(void *stream, const double *Z, int64_t n, int64_t d, int64_t n_first, int p, double eps,
                       int64_t n_sinkhorn, double *value, double *drift, double *grad, double *potentials, void *workspace,
                       size_t workspace_bytes);
+
+/* ---- differentiable sliced Wasserstein distance (pf_slicegrad.hip) ---------------------------------- */
+
+#define PFM_SLICE_LDS_ROWS 13312    /* rows per SAMPLE that pfm_slice_grad sorts itself: (float64 value, int32 row) pairs of one
+                                       sample and direction in the 160 KiB of LDS of one CU, 12 bytes each (156 KiB) */
+
+/* bytes of workspace pfm_slice_grad needs: per direction the sorted projections, their rows and the derivatives by the
+   projections, 20 bytes per direction and pooled row, and the workgroups' value partials (0: the arguments are invalid or a size
+   overflows) */
+size_t pfm_slice_grad_workspace_bytes(int64_t n, int64_t d, int64_t n_first, int64_t n_proj);
+
+/*
+ * The sliced Wasserstein distance (without the p-th root) of the pooled sample Z [n, d] (the first sample's nr = n_first rows, then
+ * the second's nf = n - n_first) over the directions theta [n_proj, d], and its row gradients.  Per direction k:
+ *   u_k[a]  = sum_j Z[a, j] theta[k, j] as pfm_project forms it (the sum starts at 0 and runs over j in order, product and sum
+ *             rounded separately).  theta may be NULL: the coordinate axes, n_proj must equal d and u_k[a] = Z[a, k], copied, so
+ *             an infinity in another feature does not reach column k;
+ *   order   each sample's rows ascending by (u_k, pooled row index): what a stable ascending sort gives;
+ *   W_k     = sum_ij ov_ij / (nr nf) |us_i - vs_j|^p over the sorted values us, vs: on a grid of nr nf cells sorted real element i
+ *             covers [i nf, (i + 1) nf), sorted fake element j covers [j nr, (j + 1) nr) and ov_ij is their overlap, positive for
+ *             nr + nf - gcd(nr, nf) pairs;
+ *   g_k     the derivative of W_k by u_k: sum_j ov_ij / (nr nf) c_ij on sorted real element i's row and -sum_i of the same on sorted
+ *             fake element j's, c = sign(us_i - vs_j) for p = 1 (exactly 0 on a coincidence), 2 (us_i - vs_j) for p = 2.  Among tied
+ *             projections the (value, index) order decides who meets whom: a valid subgradient, and deterministic.
+ *   value[0]   = (1 / n_proj) sum_k W_k
+ *   rows[a, :] = (1 / n_proj) sum_k g_k[a] theta[k, :], k ascending                = d value / d Z[a, :]
+ * perm_in NULL: the call sorts, in LDS; both samples must have at most PFM_SLICE_LDS_ROWS rows, else PFM_EUNSUPPORTED.  perm_in
+ * [n_proj, n] given: per direction the real rows in order, then the fake rows in order, as pooled row indices; it is taken as given
+ * (that it is such a permutation is the caller's duty; an entry outside [0, n) is read as the nearest row inside), for any n.
+ * rows [n, d] may be NULL: then only the value is formed.  cols_out [n_proj, n] (the projections u_k, on the pooled rows) and
+ * perm_out [n_proj, n] (the order used, laid out as perm_in) may be NULL.  theta is a constant: no derivative by it is formed.
+ * Nothing is checked for NaN or infinity: they propagate into the value, and the sort's network does not depend on the data.  No
+ * float atomics; the order of every sum depends on (n, n_first, n_proj) only, so the outputs are bitwise the same in any call.  On
+ * success every element of every output given is written.
+ * PFM_EINVAL for n < 2, d < 1, n_first outside 1 .. n - 1, n_proj outside 1 .. 65535, n >= 2^31, theta NULL with n_proj != d, a
+ * NULL Z or value; PFM_EUNSUPPORTED for a p other than 1 or 2; on any error nothing is written.
+ */
+int pfm_slice_grad(void *stream, int p, const double *Z, int64_t n, int64_t d, int64_t n_first, const double *theta,
+                   int64_t n_proj, const int32_t *perm_in, double *value, double *rows, double *cols_out, int32_t *perm_out,
+                   void *workspace, size_t workspace_bytes);
 
 /* ---- nearest-neighbour two-sample test (pf_nn.hip) ------------------------------------------------ */
 

@@ -29,6 +29,10 @@ Importing this module needs no GPU.
 sinkhorn_loss is the member of the family in between, the debiased Sinkhorn divergence of sinkhorn.py with a backward()
 (kernels: csrc/pf_sinkgrad.hip, pfm_sinkhorn_grad): its gradient is the envelope-theorem gradient, exact at the fixed point of
 the iteration and NOT the derivative of the unrolled steps; see its docstring and `drift`.
+
+sliced_wasserstein_loss and wasserstein_1d_loss are the sort-based members (kernels: csrc/pf_slicegrad.hip, pfm_slice_grad): per
+direction each sample's projections are sorted by (value, row) in LDS and coupled by quantiles, O(P n log n) where the three above
+walk n^2 pairs.  The value is mean_k W_p^p without the p-th root, for the reason energy_loss returns D^2.
 """
 import math
 
@@ -39,6 +43,8 @@ from torch.autograd.function import once_differentiable
 from . import _boot, _lib, _m1d
 
 NAMES = ("X_real", "X_fake")
+MAX_PROJECTIONS = 65535                  # pfm_slice_grad's n_proj: the directions are a grid dimension
+_MAX_LDS_ROWS = _lib.SLICE_LDS_ROWS      # rows per sample up to which pfm_slice_grad sorts itself; above, torch.sort and perm_in
 
 
 class PairLossFunction(torch.autograd.Function):
@@ -102,6 +108,59 @@ class SinkhornLossFunction(torch.autograd.Function):
         G = rows * gS
         return (None, None, None, G[:ctx.nr] if ctx.needs_input_grad[3] else None,
                 G[ctx.nr:] if ctx.needs_input_grad[4] else None)
+
+
+def _given_order(Z, nr, theta):
+    """int32 [P, N]: per direction the real rows in stable ascending order of their projections, then the fake rows, as pooled
+    row indices (pfm_slice_grad's perm_in).  pfm_project forms the projections the kernel forms: the same order, the same bytes"""
+    if theta is None:
+        cols = Z.t().contiguous()
+    else:
+        cols = torch.empty((theta.shape[0], Z.shape[0]), dtype=torch.float64, device=Z.device)
+        _lib.project(Z[:nr], Z[nr:], theta, cols)
+    first = torch.sort(cols[:, :nr], dim=1, stable=True)[1]
+    second = torch.sort(cols[:, nr:], dim=1, stable=True)[1] + nr
+    return torch.cat([first, second], dim=1).to(torch.int32).contiguous()
+
+
+def _slice_call(p, Z, nr, theta, want_rows, cols_out=None, perm_out=None):
+    """pfm_slice_grad once on the pooled rows Z [N, d] (float64, contiguous, on the device): -> (value 0-d, rows [N, d] or None).
+    theta [P, d] on the device or None (the coordinate axes).  A sample above _MAX_LDS_ROWS is ordered by torch.sort"""
+    N, d = Z.shape
+    P = d if theta is None else theta.shape[0]
+    perm_in = _given_order(Z, nr, theta) if max(nr, N - nr) > _MAX_LDS_ROWS else None
+    value = torch.empty((), dtype=torch.float64, device=Z.device)
+    rows = torch.empty_like(Z) if want_rows else None
+    ws = torch.empty(_lib.slice_grad_workspace_bytes(N, d, nr, P), dtype=torch.uint8, device=Z.device)
+    _lib.slice_grad(p, Z, nr, theta, P, perm_in, value, rows, cols_out, perm_out, ws)
+    return value, rows
+
+
+class SliceLossFunction(torch.autograd.Function):
+    """mean_k W_p^p of the pooled rows [Xr; Xf] over the directions theta (None: the coordinate axes) as one autograd node,
+    shaped like PairLossFunction.
+
+    forward : pfm_slice_grad once: the value and, if an input requires a gradient, dL/dZ [N, d], which is kept
+    backward: dL/dZ times the incoming scalar, split into the real and the fake rows; theta is a constant"""
+
+    @staticmethod
+    def forward(ctx, p, theta, Xr, Xf):
+        nr = Xr.shape[0]
+        want = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
+        Z = torch.cat([Xr.detach(), Xf.detach()], dim=0).contiguous()
+        value, rows = _slice_call(p, Z, nr, theta, want)
+        ctx.nr = nr
+        if want:
+            ctx.save_for_backward(rows)
+        return value
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gL):
+        (rows,) = ctx.saved_tensors
+        G = rows * gL
+        return (None, None, G[:ctx.nr] if ctx.needs_input_grad[2] else None,
+                G[ctx.nr:] if ctx.needs_input_grad[3] else None)
 
 
 def _gammas(bandwidth):
@@ -248,3 +307,100 @@ def sinkhorn_loss(X_real, X_fake, p=2, reg=0.1, epsilon=None, n_sinkhorn=100, st
             eps = float(epsilon)
         value, drift = SinkhornLossFunction.apply(int(p), eps, int(n_sinkhorn), Xr, Xf)
     return (value, drift) if return_drift else value
+
+
+def _check_directions(directions, d):
+    """shape and dtype checks on the caller's directions, before anything touches a device"""
+    T, shape = _boot._check_2d(directions, "directions")
+    if shape[1] != d or shape[0] > MAX_PROJECTIONS:
+        raise ValueError("directions: expected shape (P, %d) with 1 <= P <= %d, got %s" % (d, MAX_PROJECTIONS, tuple(shape)))
+    return T
+
+
+def _features(X_real, X_fake):
+    """the number of features, after the shape and dtype checks _boot.prepare makes first"""
+    sa, sb = _boot._check_2d(X_real, NAMES[0])[1], _boot._check_2d(X_fake, NAMES[1])[1]
+    if sa[1] != sb[1]:
+        raise ValueError("%s and %s have different numbers of features: %d and %d" % (NAMES[0], NAMES[1], sa[1], sb[1]))
+    return sa[1]
+
+
+def _order_p(p):
+    if not _m1d.is_int(p) or p not in (1, 2):
+        raise ValueError("p must be 1 or 2, got %r" % (p,))
+    return int(p)
+
+
+def sliced_wasserstein_loss(X_real, X_fake, n_projections=64, p=2, directions=None, standardize=False):
+    '''
+    The sliced Wasserstein distance between real and fake samples as a differentiable loss: the mean over the directions of
+    W_p^p between the two samples' projections, WITHOUT the p-th root (sliced_wasserstein_full_sample takes it), for the reason
+    energy_loss returns D^2. Per direction each sample's projections are sorted by (value, row) and coupled by quantiles: it
+    costs O(P n log n) where energy_loss, mmd_loss and sinkhorn_loss walk n^2 pairs.
+
+    Parameters:
+    -----------
+    X_real, X_fake, standardize: as energy_loss.
+    n_projections: int
+        The number of random unit directions, 1 .. 65535. Default = 64. They are ONE draw from numpy's global generator per
+        call, np.random.normal(size=(n_projections, d)) with each row divided by its 2-norm: the draw
+        sliced_wasserstein_distance makes first, so after the same np.random.seed both use the same directions.
+    p: int
+        The order, 1 or 2. Default = 2.
+    directions: None, or an array or tensor of shape [P, d], 1 <= P <= 65535
+        The directions themselves, used as given and not normalised; n_projections is then not used and nothing is drawn. A
+        training loop that wants fresh directions every step without touching the host draws them on the device. The directions
+        are constants: no gradient flows to them.
+
+    Return:
+    -------
+    0-d float64 tensor on the device, as energy_loss; with no input requiring a gradient only the value is formed. Among tied
+    projections the (value, row index) order decides which rows are matched: a valid subgradient, and deterministic; for
+    p = 1 a coincident pair adds the subgradient 0. The contents are not checked: NaN propagates into the value. A sample of
+    more than 13312 rows is ordered by torch.sort instead of the library's own sort; the result is the same bytes.
+    '''
+    _m1d.check_bool(standardize, "standardize")
+    p = _order_p(p)
+    if directions is None and (not _m1d.is_int(n_projections) or not 1 <= n_projections <= MAX_PROJECTIONS):
+        raise ValueError("n_projections must be an integer in 1 .. %d, got %r" % (MAX_PROJECTIONS, n_projections))
+    d = _features(X_real, X_fake)
+    if directions is not None:
+        directions = _check_directions(directions, d)
+    Xr, Xf = _boot.prepare(X_real, X_fake, NAMES, 1, standardize, graph=True)
+    if Xr.shape[0] + Xf.shape[0] >= 2 ** 31:
+        raise ValueError("at most 2**31 - 1 pooled samples, got %d" % (Xr.shape[0] + Xf.shape[0]))
+    with torch.cuda.device(Xr.device):
+        if directions is None:
+            from . import wasserstein                  # (the metric: its draw of the directions)
+            directions = wasserstein.directions(int(n_projections), d)
+        if not isinstance(directions, torch.Tensor):
+            directions = torch.from_numpy(np.array(directions, dtype=np.float64))        # (a copy: the caller's may be read-only)
+        theta = directions.detach().to(device=Xr.device, dtype=torch.float64).contiguous()
+        return SliceLossFunction.apply(p, theta, Xr, Xf)
+
+
+def wasserstein_1d_loss(X_real, X_fake, p=1):
+    '''
+    The 1-D Wasserstein distance of every feature as a differentiable loss: the mean over the features of W_p^p between the two
+    samples' columns, without the p-th root (wasserstein_1d's statistic of the samples as given, for p = 1). Nothing is drawn.
+    A column is the feature itself, copied: an infinity in one feature does not reach the other features' terms.
+
+    Parameters:
+    -----------
+    X_real, X_fake: as energy_loss; at most 65535 features.
+    p: int
+        The order, 1 or 2. Default = 1.
+
+    Return:
+    -------
+    0-d float64 tensor on the device, as sliced_wasserstein_loss.
+    '''
+    p = _order_p(p)
+    d = _features(X_real, X_fake)
+    if d > MAX_PROJECTIONS:
+        raise ValueError("at most %d features, got %d" % (MAX_PROJECTIONS, d))
+    Xr, Xf = _boot.prepare(X_real, X_fake, NAMES, 1, False, graph=True)
+    if Xr.shape[0] + Xf.shape[0] >= 2 ** 31:
+        raise ValueError("at most 2**31 - 1 pooled samples, got %d" % (Xr.shape[0] + Xf.shape[0]))
+    with torch.cuda.device(Xr.device):
+        return SliceLossFunction.apply(p, None, Xr, Xf)

@@ -10,6 +10,9 @@ Per iteration the rows of X_real, then of X_fake, are resampled with replacement
   sliced_wasserstein_distance  (mean_k W_p^p(Xb theta_k, Yb theta_k))^(1/p) over n_projections unit directions theta_k,
                                drawn once per call before the first bootstrap draw: np.random.normal(size=(n_projections,
                                d)) on the same generator, each row divided by its 2-norm.
+  sliced_wasserstein_full_sample  the same statistic of the samples as given, with no resampling: the directions are drawn
+                               as above and nothing else is (kernels: csrc/pf_slicegrad.hip, the value of
+                               losses.sliced_wasserstein_loss, p-th root taken).
 Inputs may be numpy arrays, array-likes or torch tensors; a CUDA tensor stays on its device.  All arithmetic is
 float64.  NaN or infinite input and a bad n_iters, p or n_projections raise ValueError before any draw.  Importing this
 module needs no GPU.
@@ -132,3 +135,31 @@ def sliced_wasserstein_distance(X_real, X_fake, n_iters=100, n_projections=64, p
     '''
     S = _replicates_sliced(X_real, X_fake, n_iters, n_projections, p, standardize)
     return S.mean(axis=0), S.std(axis=0)
+
+
+def sliced_wasserstein_full_sample(X_real, X_fake, n_projections=64, p=2, standardize=False):
+    '''
+    Calculates the sliced Wasserstein distance of the samples as given, with no resampling: the p-th root of the mean of W_p^p
+    between the samples' projections on n_projections random unit directions, drawn as sliced_wasserstein_distance draws them
+    (one np.random.normal call on numpy's global generator); nothing else is drawn.
+
+    Parameters:
+    -----------
+    X_real, X_fake, n_projections, p, standardize: as sliced_wasserstein_distance; n_projections at most 65535.
+
+    Return:
+    -------
+    The distance, numpy float64: losses.sliced_wasserstein_loss of the same directions, p-th root taken.
+    '''
+    from . import losses                               # (the loss: its kernels, value only)
+    _m1d.check_args(X_real, X_fake, 1)
+    p = _order(p)
+    n_projections = _m1d.check_positive_int(n_projections, "n_projections")
+    if n_projections > losses.MAX_PROJECTIONS:
+        raise ValueError("n_projections must be at most %d, got %d" % (losses.MAX_PROJECTIONS, n_projections))
+    _m1d.check_bool(standardize, "standardize")
+    Xr, Xf = _boot.prepare(X_real, X_fake, ("X_real", "X_fake"), 1, standardize)
+    with torch.cuda.device(Xr.device):
+        theta = torch.from_numpy(directions(n_projections, Xr.shape[1])).to(Xr.device)
+        value, _ = losses._slice_call(p, torch.cat([Xr, Xf], dim=0).contiguous(), Xr.shape[0], theta, False)
+        return _root(np.float64(value.cpu().numpy()), p)

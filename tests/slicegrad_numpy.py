@@ -1,0 +1,149 @@
+"""Float64 numpy restatement of pfm_slice_grad (probaforms_amd/metrics/csrc/pf_slicegrad.hip): the sliced Wasserstein value (no
+p-th root) of two samples over given directions and its gradient by every row.
+
+  project    u_k[a] = sum_j Z[a, j] theta[k, j] by an explicit feature loop that starts at 0, product and sum rounded separately:
+             bitwise what the kernel (and pfm_project) forms.  theta None: the coordinate axes, column k is feature k copied.
+  order      per direction np.lexsort by (value, row index) of each sample: the real rows in order, then the fake rows, as pooled
+             row indices.  What the kernel's perm_out must equal byte for byte.
+  couple     the quantile coupling in plain Python: sorted real element i against fake j = (i nf) div nr .. ((i + 1) nf - 1) div nr
+             with the overlap of [i nf, (i + 1) nf) and [j nr, (j + 1) nr) as the weight, in Python integers.
+  segments   the same pairs vectorised: the breakpoints {i nf} and {j nr} cut [0, nr nf) into nr + nf - gcd segments, each inside
+             one real and one fake element.  For shapes too large for the loop.
+value_grad returns the value, Lmag (the sum of the magnitudes of the value's terms; they are all >= 0, so Lmag is the value summed
+in this module's order), the gradient [N, d], M[a, j] = (1 / P) sum_k sum_terms |m c theta_k[j]| (the magnitudes of the terms of
+gradient element (a, j)), the projections, the order and the per-direction W_k.
+"""
+import math
+
+import numpy as np
+
+ROWS = [(1, 1), (2, 1), (1, 5), (2, 3), (63, 65), (64, 64), (65, 63), (1023, 1025), (1024, 1024), (1025, 1023), (100, 37),
+        (37, 100)]
+MIDDLE = (65, 63)
+FEATURES = (1, 2, 16, 17)
+PROJECTIONS = (1, 3, 64, 65)
+
+
+def make(nr, nf, d, seed=0):
+    """generic data: two Gaussian samples, the fake one shifted and scaled"""
+    rng = np.random.RandomState(1000 * nr + 10 * nf + d + seed)
+    Xr = rng.normal(size=(nr, d))
+    Xf = 0.7 * rng.normal(size=(nf, d)) + 0.5
+    return Xr, Xf
+
+
+def unit_directions(P, d, seed=0):
+    rng = np.random.RandomState(7919 * P + d + seed)
+    th = rng.normal(size=(P, d))
+    return th / np.sqrt((th * th).sum(axis=1))[:, None]
+
+
+def project(Z, theta):
+    """[P, N]"""
+    if theta is None:
+        return np.ascontiguousarray(Z.T)
+    P, d = theta.shape
+    cols = np.zeros((P, Z.shape[0]))
+    for k in range(P):
+        for j in range(d):
+            cols[k] = cols[k] + Z[:, j] * theta[k, j]
+    return cols
+
+
+def order(cols, nr):
+    """[P, N] int32: per direction the real rows by (value, index), then the fake rows, as pooled indices"""
+    P, N = cols.shape
+    perm = np.empty((P, N), dtype=np.int32)
+    for k in range(P):
+        perm[k, :nr] = np.lexsort((np.arange(nr), cols[k, :nr]))
+        perm[k, nr:] = nr + np.lexsort((np.arange(N - nr), cols[k, nr:]))
+    return perm
+
+
+def _c(diff, p):
+    return np.sign(diff) if p == 1 else 2.0 * diff
+
+
+def couple(us, vs, p):
+    """plain Python.  -> (W, Wmag, gu, gv, mu, mv, terms): the value, the sum of its terms' magnitudes, the derivative by every
+    sorted element, the sums of the magnitudes of their terms, and the number of terms"""
+    nr, nf = len(us), len(vs)
+    cells = nr * nf
+    W = Wmag = 0.0
+    gu, gv, mu, mv = np.zeros(nr), np.zeros(nf), np.zeros(nr), np.zeros(nf)
+    terms = 0
+    for i in range(nr):
+        lo, hi = i * nf, (i + 1) * nf
+        for j in range(lo // nr, (hi - 1) // nr + 1):
+            ov = min(hi, (j + 1) * nr) - max(lo, j * nr)
+            assert ov > 0
+            m = ov / cells
+            diff = us[i] - vs[j]
+            t = m * abs(diff) ** p
+            W += t
+            Wmag += abs(t)
+            c = float(_c(diff, p))
+            gu[i] += m * c
+            gv[j] -= m * c
+            mu[i] += abs(m * c)
+            mv[j] += abs(m * c)
+            terms += 1
+    return W, Wmag, gu, gv, mu, mv, terms
+
+
+def segments(nr, nf):
+    """(i, j, ov) int64 arrays of the nr + nf - gcd pairs with a positive overlap, ascending"""
+    cuts = np.union1d(np.arange(nr + 1, dtype=np.int64) * nf, np.arange(nf + 1, dtype=np.int64) * nr)
+    start, ov = cuts[:-1], np.diff(cuts)
+    return start // nf, start // nr, ov
+
+
+def couple_segments(us, vs, p):
+    """couple(), vectorised"""
+    nr, nf = len(us), len(vs)
+    i, j, ov = segments(nr, nf)
+    m = ov / float(nr * nf)
+    diff = us[i] - vs[j]
+    t = m * np.abs(diff) ** p
+    mc = m * _c(diff, p)
+    gu, gv = np.bincount(i, mc, nr), -np.bincount(j, mc, nf)
+    mu, mv = np.bincount(i, np.abs(mc), nr), np.bincount(j, np.abs(mc), nf)
+    return float(t.sum()), float(np.abs(t).sum()), gu, gv, mu, mv, len(i)
+
+
+def value_grad(Xr, Xf, theta, p, vectorised=False):
+    """theta [P, d] or None (the coordinate axes)"""
+    Z = np.concatenate([Xr, Xf])
+    nr, (N, d) = len(Xr), Z.shape
+    cols = project(Z, theta)
+    perm = order(cols, nr)
+    P = cols.shape[0]
+    W, value, Lmag, terms = np.empty(P), 0.0, 0.0, 0
+    g, mag = np.zeros((P, N)), np.zeros((P, N))
+    for k in range(P):
+        us, vs = cols[k, perm[k, :nr]], cols[k, perm[k, nr:]]
+        W[k], Wmag, gu, gv, mu, mv, t = (couple_segments if vectorised else couple)(us, vs, p)
+        g[k, perm[k, :nr]], g[k, perm[k, nr:]] = gu, gv
+        mag[k, perm[k, :nr]], mag[k, perm[k, nr:]] = mu, mv
+        value += W[k] / P
+        Lmag += Wmag / P
+        terms += t
+    assert terms == P * (N - math.gcd(nr, N - nr))
+    if theta is None:                       # column k is feature k alone: nothing of it reaches another feature
+        grad, M = g.T / P, mag.T / P
+    else:
+        grad = np.zeros((N, d))
+        for k in range(P):
+            grad = grad + g[k][:, None] * theta[k][None, :] / P
+        M = (mag.T @ np.abs(theta)) / P
+    return {"value": value, "Lmag": Lmag, "grad": grad, "M": M, "cols": cols, "perm": perm, "W": W, "g": g}
+
+
+def torch_value(Xr, Xf, theta, p):
+    """float64 torch autograd version for nr == nf: the sorted samples are matched one to one (torch tensors in, 0-d out)"""
+    import torch
+    assert Xr.shape[0] == Xf.shape[0]
+    us = torch.sort(Xr @ theta.t(), dim=0)[0]
+    vs = torch.sort(Xf @ theta.t(), dim=0)[0]
+    diff = us - vs
+    return (diff.abs() if p == 1 else diff * diff).mean()
