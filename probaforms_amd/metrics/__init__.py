@@ -30,6 +30,11 @@ fills the gradient of the generated (or the real) rows, from one more sweep over
 
     from probaforms_amd.metrics.losses import energy_loss, mmd_loss       # differentiable D^2 and biased MMD^2
 
+Those compare two pooled samples.  The loss a CONDITIONAL sampler is trained on scores every condition row's K draws against the
+row's own observed target, the energy score and the CRPS that sample_joint_scores and sample_scores report as metrics:
+
+    from probaforms_amd.metrics.losses import energy_score_loss, crps_loss    # X_draws [K, n, d] against Y [n, d], per row
+
 `__all__` and the `probaforms.metrics` alias (`probaforms_amd.install_as_probaforms()`) name only the two
 multivariate metrics, so `from probaforms.metrics import kolmogorov_smirnov_1d` raises ImportError there.
 """

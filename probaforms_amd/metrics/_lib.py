@@ -25,6 +25,8 @@ PERM_ENERGY, PERM_GAUSS = 0, 1   # PFM_PERM_*: the pair value of pfm_perm_form
 KEY_MASK_ALL = 2 ** 64 - 1 # pfm_perm_labels' key_mask in use: all 64 key bits count
 PAIR_MAX_GAMMAS = 8        # PFM_PAIR_MAX_GAMMAS: Gaussians in pfm_pair_grad's kernel sum
 SLICE_LDS_ROWS = 13312     # PFM_SLICE_LDS_ROWS: rows per sample pfm_slice_grad sorts itself, in LDS
+SCORE_MAX_K = 1024         # PFM_SCORE_MAX_K: draws per row of pfm_score_grad
+SCORE_MAX_KD = 16384       # PFM_SCORE_MAX_KD: draws times features of pfm_score_grad (a row's draws in LDS)
 PFM_EINVAL, PFM_EUNSUPPORTED, PFM_EWORKSPACE = -1, -2, -3
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -66,6 +68,9 @@ _SIGNATURES = {
     "pfm_sinkhorn_grad": (C.c_int, [_VP, _VP, _I64, _I64, _I64, C.c_int, C.c_double, _I64, _VP, _VP, _VP, _VP, _VP, _SZ]),
     "pfm_slice_grad_workspace_bytes": (_SZ, [_I64, _I64, _I64, _I64]),
     "pfm_slice_grad": (C.c_int, [_VP, C.c_int, _VP, _I64, _I64, _I64, _VP, _I64, _VP, _VP, _VP, _VP, _VP, _VP, _SZ]),
+    "pfm_score_grad_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
+    "pfm_score_plan": (C.c_int, [_I64, _I64, _I64, _VP]),
+    "pfm_score_grad": (C.c_int, [_VP, _VP, _VP, _I64, _I64, _I64, C.c_int, _VP, _VP, _VP, _VP, _VP, _SZ]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -383,3 +388,39 @@ def slice_grad_status(p, Z, n_first, theta, n_proj, perm_in, value, rows, cols_o
 
 def slice_grad(*args):
     check(slice_grad_status(*args), "pfm_slice_grad")
+
+
+def score_grad_workspace_bytes(n, K, d):
+    return int(lib().pfm_score_grad_workspace_bytes(int(n), int(K), int(d)))
+
+
+def score_plan_status(n, K, d):
+    """-> (status, (rows per workgroup, lanes that share a row, LDS bytes, workgroups)): how pfm_score_grad tiles a call; no
+    device is touched"""
+    plan = (C.c_int64 * 4)()
+    st = int(lib().pfm_score_plan(int(n), int(K), int(d), C.cast(plan, _VP)))
+    return st, tuple(int(v) for v in plan)
+
+
+def score_plan(n, K, d):
+    st, plan = score_plan_status(n, K, d)
+    check(st, "pfm_score_plan")
+    return plan
+
+
+def score_grad_status(X, Y, fair, scores, spread, grad_x, grad_y, ws):
+    """enqueue the per-row energy scores [n] of the draws X [K, n, d] against the targets Y [n, d] and, where given, the spread
+    [n] and the derivatives grad_x [K, n, d], grad_y [n, d] on the current stream and return the status"""
+    K, n, d = X.shape
+    assert tuple(Y.shape) == (n, d) and scores.numel() == n and (spread is None or spread.numel() == n)
+    assert (grad_x is None or tuple(grad_x.shape) == (K, n, d)) and (grad_y is None or tuple(grad_y.shape) == (n, d))
+    return int(lib().pfm_score_grad(torch.cuda.current_stream().cuda_stream, _ptr(X, torch.float64, "X_draws"),
+                                    _ptr(Y, torch.float64, "Y"), n, K, d, int(bool(fair)), _ptr(scores, torch.float64, "scores"),
+                                    _ptr(spread, torch.float64, "spread", nullable=True),
+                                    _ptr(grad_x, torch.float64, "grad_x", nullable=True),
+                                    _ptr(grad_y, torch.float64, "grad_y", nullable=True), _ptr(ws, torch.uint8, "workspace"),
+                                    ws.numel()))
+
+
+def score_grad(*args):
+    check(score_grad_status(*args), "pfm_score_grad")

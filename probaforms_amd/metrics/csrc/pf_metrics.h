@@ -39,6 +39,9 @@
  *   pfm_slice_grad    the sliced Wasserstein distance of the samples as given TOGETHER WITH its derivative by every row: per
  *                     direction a (value, row) sort of each sample in LDS, the quantile coupling of the two sorted samples and
  *                     its gradient, O(P n log n) where the three above walk n^2 pairs
+ *   pfm_score_grad    per row, the energy score of the row's K draws against the row's target TOGETHER WITH its derivative by
+ *                     every draw and by the target: the loss a conditional sampler is trained on, one sweep over each row's
+ *                     K (K - 1) / 2 pairs in LDS; pfm_score_plan says how a shape is tiled
  *
  * Conventions (as include/rnvp_hip.h)
  *   - every pointer is a DEVICE pointer (but pfm_pair_grad's `gammas`); sizes are plain integers;
@@ -386,6 +389,50 @@ size_t pfm_slice_grad_workspace_bytes(int64_t n, int64_t d, int64_t n_first, int
 int pfm_slice_grad(void *stream, int p, const double *Z, int64_t n, int64_t d, int64_t n_first, const double *theta,
                    int64_t n_proj, const int32_t *perm_in, double *value, double *rows, double *cols_out, int32_t *perm_out,
                    void *workspace, size_t workspace_bytes);
+
+/* ---- differentiable per-row scoring rule: the energy score of K draws (pf_scoregrad.hip) ------------ */
+
+#define PFM_SCORE_MAX_K 1024        /* draws per row of pfm_score_grad: a lane owns at most four of them */
+#define PFM_SCORE_MAX_KD 16384      /* K d of pfm_score_grad: a row's draws as float64 in 128 KiB of the 160 KiB of LDS of one CU */
+
+/* bytes of workspace pfm_score_grad needs: nothing is kept there, the figure is the least a caller can allocate (0: the arguments
+   are invalid or outside the limits) */
+size_t pfm_score_grad_workspace_bytes(int64_t n, int64_t K, int64_t d);
+
+/*
+ * How pfm_score_grad tiles a call of n rows, K draws and d features; needs no device.  plan is a HOST array of 4:
+ *   plan[0]  R: the consecutive rows of a workgroup (for every draw, one contiguous run of R d doubles of X and of grad_x)
+ *   plan[1]  S: the lanes that share one row, a power of two, min(256, the least >= K); 256 / S rows are in flight at a time
+ *            (fewer where LDS holds fewer), and a lane owns ceil(K / S) draws.  S < 256: rows packed into the waves (the
+ *            streaming regime of a few draws); S = 256: a workgroup per row at a time (the pair walk of many draws)
+ *   plan[2]  the dynamic LDS bytes of a workgroup, at most 163840
+ *   plan[3]  the workgroups, ceil(n / R)
+ * R depends on n (fewer rows per workgroup while the workgroups are few); no output of pfm_score_grad does.
+ * The statuses are pfm_score_grad's for the sizes; PFM_EINVAL for a NULL plan.
+ */
+int pfm_score_plan(int64_t n, int64_t K, int64_t d, int64_t *plan);
+
+/*
+ * The energy score (Gneiting & Raftery 2007) of every row's K draws against the row's target, and its derivatives.  X [K, n, d]
+ * holds draw k of row i at X[k, i, :], Y [n, d] the targets.  Per row, with x_k = X[k, i, :], y = Y[i, :] and D = K - 1 if fair
+ * else K:
+ *   T1        = (1 / K) sum_k |x_k - y|_2
+ *   spread[i] = 1 / (2 K D) sum_k sum_l |x_k - x_l|_2           (every unordered pair's distance is formed once)
+ *   scores[i] = T1 - spread[i]
+ *   grad_x[k, i, :] = (1 / K) c_k (x_k - y) - (1 / (K D)) sum_l c_kl (x_k - x_l)        = d scores[i] / d X[k, i, :]
+ *   grad_y[i, :]    = -(1 / K) sum_k c_k (x_k - y)                                      = d scores[i] / d Y[i, :]
+ * c = 1 / distance and exactly 0 where the squared distance is exactly 0 (the subgradient); the squared distance is
+ * fma(df, df, acc) over the features in order, df the difference of the values themselves: no norm / dot-product identity, so
+ * draws centred far from the origin lose nothing and duplicated draws add exactly 0 to each other.
+ * spread [n], grad_x [K, n, d] and grad_y [n, d] may each be NULL; with both gradients NULL only the values are formed.
+ * Nothing is checked for NaN or infinity: they propagate inside their row and reach no other row.  No float atomics, and nothing is
+ * kept in the workspace; the order of every sum depends on (K, d) only, so a row's outputs are bitwise the same at any position of
+ * the row, for any n, in any call.  On success every element of every output given is written.
+ * PFM_EINVAL for n, K or d < 1, n >= 2^31, fair != 0 with K = 1, a NULL X, Y or scores; PFM_EUNSUPPORTED for K > PFM_SCORE_MAX_K
+ * or K d > PFM_SCORE_MAX_KD; PFM_EWORKSPACE for a missing or short workspace; on any error nothing is written.
+ */
+int pfm_score_grad(void *stream, const double *X, const double *Y, int64_t n, int64_t K, int64_t d, int fair, double *scores,
+                   double *spread, double *grad_x, double *grad_y, void *workspace, size_t workspace_bytes);
 
 /* ---- nearest-neighbour two-sample test (pf_nn.hip) ------------------------------------------------ */
 

@@ -33,6 +33,12 @@ the iteration and NOT the derivative of the unrolled steps; see its docstring an
 sliced_wasserstein_loss and wasserstein_1d_loss are the sort-based members (kernels: csrc/pf_slicegrad.hip, pfm_slice_grad): per
 direction each sample's projections are sorted by (value, row) in LDS and coupled by quantiles, O(P n log n) where the three above
 walk n^2 pairs.  The value is mean_k W_p^p without the p-th root, for the reason energy_loss returns D^2.
+
+energy_score_loss and crps_loss are the CONDITIONAL members (kernel: csrc/pf_scoregrad.hip, pfm_score_grad): per condition row the
+energy score (Gneiting & Raftery 2007) of the row's K draws against the row's observed target, the strictly proper scoring rule
+sample_joint_scores and sample_scores report as metrics, with a backward().  The four above compare two pooled samples; these give
+every row its own signal and cost K^2 pairs per row, not n^2.  Value and gradients come from one sweep over each row's pairs in LDS;
+nothing of size K^2 is stored, for the forward or for the backward.
 """
 import math
 
@@ -161,6 +167,32 @@ class SliceLossFunction(torch.autograd.Function):
         G = rows * gL
         return (None, None, G[:ctx.nr] if ctx.needs_input_grad[2] else None,
                 G[ctx.nr:] if ctx.needs_input_grad[3] else None)
+
+
+class ScoreFunction(torch.autograd.Function):
+    """The per-row energy scores [n] of the draws X [K, n, d] against the targets Y [n, d] as one autograd node.
+
+    forward : pfm_score_grad once: the scores and, for whichever of X and Y requires a gradient, the unscaled per-row derivatives
+              d scores[i] / d X[:, i, :] and d scores[i] / d Y[i, :], which are kept
+    backward: those times the incoming [n] vector"""
+
+    @staticmethod
+    def forward(ctx, fair, X, Y):
+        X, Y = X.detach(), Y.detach()
+        scores = torch.empty(X.shape[1], dtype=torch.float64, device=X.device)
+        gx = torch.empty_like(X) if ctx.needs_input_grad[1] else None
+        gy = torch.empty_like(Y) if ctx.needs_input_grad[2] else None
+        ws = torch.empty(_lib.score_grad_workspace_bytes(X.shape[1], X.shape[0], X.shape[2]), dtype=torch.uint8, device=X.device)
+        _lib.score_grad(X, Y, fair, scores, None, gx, gy, ws)
+        ctx.save_for_backward(gx, gy)
+        return scores
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gS):
+        gx, gy = ctx.saved_tensors
+        return (None, gx * gS[None, :, None] if ctx.needs_input_grad[1] else None,
+                gy * gS[:, None] if ctx.needs_input_grad[2] else None)
 
 
 def _gammas(bandwidth):
@@ -404,3 +436,116 @@ def wasserstein_1d_loss(X_real, X_fake, p=1):
         raise ValueError("at most 2**31 - 1 pooled samples, got %d" % (Xr.shape[0] + Xf.shape[0]))
     with torch.cuda.device(Xr.device):
         return SliceLossFunction.apply(p, None, Xr, Xf)
+
+
+def _check_nd(A, name, rank, what):
+    """shape and dtype checks on the caller's object, before anything touches a device"""
+    if isinstance(A, torch.Tensor):
+        if A.is_complex() or A.dtype == torch.bool:
+            raise ValueError("%s: expected a real numeric tensor, got %s" % (name, A.dtype))
+        shape = tuple(A.shape)
+    else:
+        A = np.asarray(A)
+        if A.dtype.kind not in "fiu":
+            raise ValueError("%s: expected a real numeric array, got dtype %s" % (name, A.dtype))
+        shape = A.shape
+    if len(shape) != rank:
+        raise ValueError("%s: expected a %d-D array %s, got shape %s" % (name, rank, what, tuple(shape)))
+    if min(shape) < 1:
+        raise ValueError("%s: expected at least one draw, one row and one feature, got shape %s" % (name, tuple(shape)))
+    return A, tuple(shape)
+
+
+def _score_inputs(X_draws, Y, fair, reduction, per_feature):
+    """the checks, all before a device is touched -> (X [K, n, d], Y [n, d], Y's shape as given): contiguous float64 tensors on one
+    HIP device, in their autograd graph; per_feature: every (row, feature) series becomes a row of one feature"""
+    _m1d.check_bool(fair, "fair")
+    if reduction not in ("mean", "none"):
+        raise ValueError("reduction must be 'mean' or 'none', got %r" % (reduction,))
+    X, sx = _check_nd(X_draws, "X_draws", 3, "[n_draws, n_samples, n_features]")
+    Yt, sy = _check_nd(Y, "Y", 2, "[n_samples, n_features]")
+    K, n, d = sx
+    if sy != (n, d):
+        raise ValueError("X_draws and Y have different numbers of samples or features: %s and %s" % (sx, sy))
+    if per_feature:
+        n, d = n * d, 1
+    if fair and K == 1:
+        raise ValueError("fair=True needs at least 2 draws per row (the spread is divided by K - 1), got 1")
+    if K > _lib.SCORE_MAX_K or K * d > _lib.SCORE_MAX_KD:
+        raise ValueError("at most %d draws per row and %d draws times features, got K = %d, d = %d"
+                         % (_lib.SCORE_MAX_K, _lib.SCORE_MAX_KD, K, d))
+    if n >= 2 ** 31:
+        raise ValueError("at most 2**31 - 1 rows, got %d" % n)
+    if not torch.cuda.is_available():
+        raise RuntimeError("probaforms_amd.metrics runs on a HIP device and none is visible (there is no CPU fallback)")
+    dev = next((t.device for t in (X, Yt) if isinstance(t, torch.Tensor) and t.is_cuda),
+               torch.device("cuda", torch.cuda.current_device()))
+
+    def dev64(t, shape):
+        if not isinstance(t, torch.Tensor):
+            t = torch.from_numpy(np.array(t, dtype=np.float64))                      # (a copy: the caller's may be read-only)
+        return t.to(device=dev, dtype=torch.float64).contiguous().reshape(shape)        # torch ops: the graph carries them
+    return dev64(X, (K, n, d)), dev64(Yt, (n, d)), sy
+
+
+def _score_loss(X_draws, Y, fair, reduction, per_feature):
+    X, Yt, shape = _score_inputs(X_draws, Y, fair, reduction, per_feature)
+    with torch.cuda.device(X.device):
+        scores = ScoreFunction.apply(bool(fair), X, Yt)
+        if reduction == "mean":
+            return scores.mean()
+        return scores.reshape(shape) if per_feature else scores
+
+
+def energy_score_loss(X_draws, Y, fair=True, reduction="mean"):
+    '''
+    The energy score (Gneiting & Raftery 2007) of K draws per condition row against the row's observed target, as a
+    differentiable loss: per row ES = (1/K) sum_k |x_k - y| - 1/(2 K D) sum_k sum_l |x_k - x_l|, |.| the Euclidean norm, the
+    `energy` of sample_joint_scores. Minimising its mean over a batch is a strictly proper objective for any conditional sampler
+    (scoring-rule minimisation, "engression"): X_draws = model.nf.sample(C.repeat(K, 1)).view(K, n, d).
+
+    Parameters:
+    -----------
+    X_draws: array of shape [n_draws, n_samples, n_features] (numpy, array-like or torch; a CUDA tensor stays on the device)
+        Draw k of row i is X_draws[k, i], as sample_many returns them; for training, a tensor that requires a gradient. At most
+        1024 draws and 16384 draws times features.
+    Y: array of shape [n_samples, n_features]
+        The observed targets.
+    fair: boolean
+        If True, D = K - 1 (the unbiased spread; needs K >= 2), else D = K. Default = True, which DIFFERS from
+        sample_joint_scores, a metric: used as a loss, the biased D = K form halves the spread at K = 2 and trains
+        under-dispersed samplers. fair=False with K = 1 is the mean Euclidean error.
+    reduction: "mean" or "none"
+        "mean": the mean over the rows, a 0-d tensor. "none": the [n_samples] per-row scores, for a weighted sum. Default =
+        "mean".
+
+    Return:
+    -------
+    float64 tensor on the device. backward() fills the gradients of whichever of X_draws and Y require one (float32 inputs get
+    float32 gradients); with none only the scores are formed and the result has no grad_fn. A coincident pair of draws, or a
+    draw equal to its target, adds the subgradient 0. The contents are not checked: a NaN in a row's draws or target makes
+    that row's score and gradients NaN and touches no other row. With device tensors nothing waits for the device.
+    '''
+    return _score_loss(X_draws, Y, fair, reduction, False)
+
+
+def crps_loss(X_draws, Y, fair=True, reduction="mean"):
+    '''
+    The continuous ranked probability score of K draws per condition row and feature against the observed value, as a
+    differentiable loss: the energy score of every (row, feature) series on its own, at n_features = 1 the `crps` of
+    sample_scores. The same kernel call as energy_score_loss on X_draws.reshape(K, n d, 1) and Y.reshape(n d, 1).
+
+    It walks the K (K - 1) / 2 pairs of every series, O(K^2). The sorted O(K log K) route of sample_scores has no gradient here;
+    a sorted route with a gradient is not provided.
+
+    Parameters:
+    -----------
+    X_draws, Y, fair: as energy_score_loss; at most 1024 draws.
+    reduction: "mean" or "none"
+        "mean": the mean over rows and features, a 0-d tensor. "none": the [n_samples, n_features] scores. Default = "mean".
+
+    Return:
+    -------
+    float64 tensor on the device, as energy_score_loss.
+    '''
+    return _score_loss(X_draws, Y, fair, reduction, True)
