@@ -25,7 +25,13 @@ FEATURES = (1, 16, 17, 33)                                   # one chunk of 16 f
 CASES = [(nr, nf, d, "plain") for nr, nf in ROWS for d in FEATURES]
 CASES += [(1200, 1000, 2, "plain"), (1200, 1000, 17, "plain")]           # several column slices, many workgroups
 CASES += [(65, 63, 17, "copies"), (130, 70, 2, "copies"), (40, 50, 5, "far"), (65, 63, 17, "far")]
-HOST_ONLY_CASES = [(1, 1, 1, "plain"), (2, 1, 3, "plain")]               # the smallest shapes there are
+# where the sweeps' axes cross (tests/loss_plans.py names the cells, tests/test_loss_plans_host.py proves they are reached): a
+# workgroup that walks several column tiles with the features re-staged per tile (d > 16, tiles per slice 2), the same with a full
+# middle feature chunk and a ragged last slice (d = 33: 3 chunks, 10 slices of 2 over 19 tiles), the same with one chunk resident
+# (d = 5; 33 tiles is the fewest that share a slice), and one row of one sample against several tiles of the other, both ways
+CROSSED = [(760, 713, 17, "plain"), (600, 560, 33, "plain"), (1040, 1010, 5, "plain"), (1, 130, 2, "plain"), (130, 1, 17, "plain")]
+CASES += CROSSED
+HOST_ONLY_CASES =[(1, 1, 1, "plain"), (2, 1, 3, "plain")]               # the smallest shapes there are
 
 
 def case_id(case):

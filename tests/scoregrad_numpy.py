@@ -57,6 +57,41 @@ def score_of(X, Y, fair):
 # the rows the tests feed
 # ---------------------------------------------------------------------------------------------------------------------------
 
+# (K, n, d) where the kernel's shape axes cross: every k_score instantiation and plan branch that one axis at a time leaves out
+# (tests/loss_plans.py names them; tests/test_loss_plans_host.py proves the list reaches them).  Each is the smallest shape of its path
+CROSSED = [
+    (300, 3, 16),      # U = 2, 16 features in registers
+    (300, 3, 17),      # U = 2, chunked
+    (512, 3, 32),      # U = 2, chunked, 151 816 bytes of LDS
+    (600, 3, 1),       # U = 4 with a masked draw slot, one feature
+    (1024, 3, 1),      # U = 4 with all four slots live, one feature
+    (600, 3, 17),      # U = 4 masked, chunked
+    (770, 3, 21),      # U = 4 full, chunked, 152 112 bytes of LDS
+    (1, 3, 16384),     # the target read from global memory, even pitch, chunked
+    (2, 3, 8192),
+    (4, 3, 4096),
+    (5, 3, 3276),      # the neighbour whose target is staged again: G = 1, seven eighths of the lanes idle
+    (64, 9, 100),      # G 4 -> 2 for the LDS; n odd: the last workgroup has one row
+    (16, 40, 100),     # G 16 -> 8
+    (128, 3, 128),     # G 2 -> 1
+    (33, 2051, 17),    # several passes per workgroup, chunked
+]
+CROSSED_NAN = [(300, 7, 17), (4, 7, 4096)]
+CROSSED_LAYOUT = [(300, 5, 17), (4, 3, 4096)]
+
+
+RTOL = 1e-12
+U53 = 2.0 ** -53
+
+
+def rtol_of(d):
+    """the bound on an output computed in another order, in units of the sum of its terms' magnitudes.  RTOL covers the sums of up
+    to 1088 terms and "a few 2^-53" per term.  The latter does not hold where a distance sums thousands of squares: a sum of d
+    non-negative squares taken in any order is within d 2^-53 of itself relatively, the square root halves that and the reciprocal
+    keeps it, and every term of every output is such a distance or a difference over one.  So d 2^-53 is added for d > 128"""
+    return RTOL + (d * U53 if d > 128 else 0.0)
+
+
 def rows(K, n, d, seed=0):
     """generic rows: a conditional Gaussian sampler's draws, x_k = mu_i + sigma_i eps_k, and targets from a shifted law; no two
     points of a row coincide"""

@@ -22,6 +22,10 @@ ROWS = [(1, 1), (2, 1), (1, 5), (2, 3), (63, 65), (64, 64), (65, 63), (1023, 102
 MIDDLE = (65, 63)
 FEATURES = (1, 2, 16, 17)
 PROJECTIONS = (1, 3, 64, 65)
+# (nr, nf, d, P) where the axes cross: three blocks of 256 rows by two chunks of 16 features by two groups of 8 directions, the
+# second ragged; one element against a whole sample, both ways.  And the coordinate-axes route over several row blocks and groups
+CROSSED = [(300, 250, 17, 9), (1, 1025, 2, 3), (1025, 1, 2, 3)]
+CROSSED_AXES = [(300, 250, 17)]
 
 
 def make(nr, nf, d, seed=0):
@@ -140,10 +144,16 @@ def value_grad(Xr, Xf, theta, p, vectorised=False):
 
 
 def torch_value(Xr, Xf, theta, p):
-    """float64 torch autograd version for nr == nf: the sorted samples are matched one to one (torch tensors in, 0-d out)"""
+    """float64 torch autograd version (torch tensors in, 0-d out; theta None: the coordinate axes).  nr == nf: the sorted samples
+    are matched one to one; else the sorted elements of segments() are, with the segments' share of the nr nf cells as weights"""
     import torch
-    assert Xr.shape[0] == Xf.shape[0]
-    us = torch.sort(Xr @ theta.t(), dim=0)[0]
-    vs = torch.sort(Xf @ theta.t(), dim=0)[0]
-    diff = us - vs
-    return (diff.abs() if p == 1 else diff * diff).mean()
+    us = torch.sort(Xr if theta is None else Xr @ theta.t(), dim=0)[0]
+    vs = torch.sort(Xf if theta is None else Xf @ theta.t(), dim=0)[0]
+    nr, nf = Xr.shape[0], Xf.shape[0]
+    if nr == nf:
+        diff = us - vs
+        return (diff.abs() if p == 1 else diff * diff).mean()
+    i, j, ov = segments(nr, nf)
+    diff = us[torch.from_numpy(i)] - vs[torch.from_numpy(j)]
+    m = torch.from_numpy(ov / float(nr * nf))[:, None]
+    return (m * (diff.abs() if p == 1 else diff * diff)).sum(dim=0).mean()

@@ -7,11 +7,19 @@ terms, from the restatement: a float64 sum of at most 1024 + 64 correctly rounde
 1088 2^-53 = 1.2e-13 of that sum, and a term (a square root, a reciprocal, a product) carries a few 2^-53 of its own: two orders
 below the bound.  Where the magnitudes are 0 (every term coincident) the output must be exactly 0.  The largest ratios seen are
 printed by test_zz_largest_deviation.
+"A term carries a few 2^-53" does not hold where a distance sums thousands of squares, so for d > 128 the bound per output is
+(1e-12 + d 2^-53) of the magnitudes: a sum of d non-negative squares taken in any order (the kernel's is an fma chain, the
+restatement's numpy's pairwise sum) is within d 2^-53 of itself relatively; the square root halves that and the reciprocal keeps
+it, and every term of every output is a distance or a difference over a distance.  rtol_of states it.  Seen on an MI355X for the
+crossed-axes cases (scoregrad_numpy.CROSSED and its NaN and layout shapes): at most 0.0031 of their bound for grad_x, 0.0019 for
+grad_y, 0.0014 for the spread and 0.0009 for the scores, that is 4e-15 of the magnitudes at the most.
 
 Shapes: K in 1, 2, 3, 31, 32, 33, 63, 64, 65, 257 and every K at which pfm_score_plan changes the lanes per row or the draws per
 lane, with K + 1, at d = 2; d in 1, 2, 16, 17, 33 (one chunk of 16 features, its edge, three chunks) at K = 33; n in 1, 2, R - 1, R,
 R + 1, 3 R + 1 at K = 3, d = 2, and two shapes whose n is large enough for several passes per workgroup; the limit shapes
-K = 1024, d = 16 and K = 256, d = 64.
+K = 1024, d = 16 and K = 256, d = 64.  scoregrad_numpy.CROSSED crosses the axes: every k_score instantiation (draws per lane 1, 2, 4 by
+1, 4, 16 features in registers or chunks) and every branch of the host's plan (the target left in global memory, even pitches,
+rows in flight halved for the LDS, idle lanes, several chunked passes), as tests/test_loss_plans_host.py proves.
 """
 import functools
 import os
@@ -54,13 +62,23 @@ R3 = _lib.score_plan(1, 3, 2)[0]
 # (K, n, d)
 CASES = [(K, 7, 2) for K in KS] + [(33, 7, d) for d in (1, 2, 16, 17, 33)]
 CASES += [(3, n, 2) for n in (1, 2, R3 - 1, R3, R3 + 1, 3 * R3 + 1)]
-PASSES = [(33, 2051, 2), (129, 769, 2)]                     # n so large that a workgroup takes its rows in several passes
+PASSES = [(33, 2051, 2), (129, 769, 2), (33, 2051, 17)]     # n so large that a workgroup takes its rows in several passes
 LIMITS = [(1024, 3, 16), (256, 3, 64)]
-CASES = sorted(set(CASES)) + PASSES + LIMITS
+CASES = sorted(set(CASES)) + PASSES[:2] + LIMITS + sg.CROSSED
+assert PASSES[2] in sg.CROSSED and len(set(CASES)) == len(CASES)
+NAN_CASES = [(3, R3 + 6, 2), (33, 7, 17), (257, 7, 2)] + sg.CROSSED_NAN
+POSITION_CASES = [(3, 3 * R3 + 1, 2), (33, 2051, 2), (257, 7, 2), (33, 7, 17)] + sg.CROSSED_LAYOUT
+WORKSPACE_CASES = [(3, R3 + 1, 2), (33, 5, 17), (257, 3, 2), (2, 1, 1)] + sg.CROSSED_LAYOUT
+NEW = set(sg.CROSSED + sg.CROSSED_NAN + sg.CROSSED_LAYOUT)
+WORST_NEW = {name: 0.0 for name, _ in OUTPUTS}              # of the bound, over the cases of NEW
 
 
 def case_id(case):
     return "K%d_n%d_d%d" % case
+
+
+rtol_of = sg.rtol_of             # RTOL, and d 2^-53 more where a distance sums more than 128 squares (derived beside it)
+assert rtol_of(128) == RTOL and rtol_of(4096) == RTOL + 4096 * U53
 
 
 def dev(A, grad=False, dtype=torch.float64):
@@ -95,16 +113,19 @@ def raw(X, Y, fair, spread=True, gx=True, gy=True):
     return {k: v.cpu().numpy() for k, v in out.items()}
 
 
-def assert_close(got, want, what):
+def assert_close(got, want, what, case=None):
+    rtol = RTOL if case is None else rtol_of(case[2])
     for name, mag in OUTPUTS:
         if name not in got:
             continue
         err, m = np.abs(got[name] - want[name]), np.abs(want[mag])
         rel = float((err / np.where(m > 0, m, 1.0)).max())
         WORST[name] = max(WORST[name], rel)
-        print("%s: %s off by at most %.3g of its terms' magnitudes" % (what, name, rel))
+        if case in NEW:
+            WORST_NEW[name] = max(WORST_NEW[name], rel / rtol)
+        print("%s: %s off by at most %.3g of its terms' magnitudes (bound %.3g)" % (what, name, rel, rtol))
         assert np.isfinite(got[name]).all(), (what, name)
-        assert (err <= RTOL * m).all(), (what, name, rel)
+        assert (err <= rtol * m).all(), (what, name, rel)
 
 
 # ---- accuracy ---------------------------------------------------------------------------------------------------------
@@ -123,7 +144,7 @@ def test_scores_spread_and_gradients_equal_the_restatement(case, fair):
         assert R > _lib.score_plan(1, K, d)[0]                   # several passes over the rows in flight
     X, Y, want = reference(case, fair)
     got = raw(X, Y, fair)
-    assert_close(got, want, "%s fair=%s" % (case_id(case), fair))
+    assert_close(got, want, "%s fair=%s" % (case_id(case), fair), case)
     # the value alone is formed alike
     assert raw(X, Y, fair, gx=False, gy=False)["scores"].tobytes() == got["scores"].tobytes()
     # the public function: the same kernel call behind an autograd node
@@ -173,7 +194,7 @@ def same(a, b):
     return a.tobytes() == b.tobytes()
 
 
-@pytest.mark.parametrize("case", [(3, 3 * R3 + 1, 2), (33, 2051, 2), (257, 7, 2), (33, 7, 17)], ids=case_id)
+@pytest.mark.parametrize("case", POSITION_CASES, ids=case_id)
 def test_a_rows_outputs_do_not_depend_on_n_position_or_split(case):
     K, n, d = case
     X, Y, _ = reference(case, True)
@@ -189,7 +210,7 @@ def test_a_rows_outputs_do_not_depend_on_n_position_or_split(case):
 
 
 @pytest.mark.parametrize("fair", (False, True))
-@pytest.mark.parametrize("case", [(3, R3 + 1, 2), (33, 5, 17), (257, 3, 2), (2, 1, 1)], ids=case_id)
+@pytest.mark.parametrize("case", WORKSPACE_CASES, ids=case_id)
 def test_outputs_do_not_depend_on_the_workspace_and_are_all_written(case, fair):
     K, n, d = case
     X, Y = sg.rows(K, n, d)
@@ -351,7 +372,7 @@ def test_forward_and_backward_never_wait_for_the_device():
     assert abs(float(L.detach()) - want["scores"].mean()) <= RTOL * want["smag"].mean()
 
 
-@pytest.mark.parametrize("case", [(3, R3 + 6, 2), (33, 7, 17), (257, 7, 2)], ids=case_id)
+@pytest.mark.parametrize("case", NAN_CASES, ids=case_id)
 def test_a_nan_stays_in_its_row(case):
     K, n, d = case
     X, Y = sg.rows(K, n, d)
@@ -366,7 +387,8 @@ def test_a_nan_stays_in_its_row(case):
     gx, gy = np.isnan(got["grad_x"]), np.isnan(got["grad_y"])
     assert gx[:, rows].all() and not gx[:, ~rows].any() and gy[rows].all() and not gy[~rows].any()
     clean = sg.value_grad(np.delete(X, [1, 4], axis=1), np.delete(Y, [1, 4], axis=0), True)
-    assert_close({k: np.delete(v, [1, 4], axis=1 if k == "grad_x" else 0) for k, v in got.items()}, clean, "beside NaN rows")
+    assert_close({k: np.delete(v, [1, 4], axis=1 if k == "grad_x" else 0) for k, v in got.items()}, clean, "beside NaN rows",
+                 case)
 
 
 # ---- end to end -------------------------------------------------------------------------------------------------------
@@ -439,3 +461,5 @@ def test_forward_and_backward_keep_nothing_of_the_size_of_the_pairs():
 def test_zz_largest_deviation():
     print("largest deviation seen, in units of the terms' magnitudes (bound %.3g): %s"
           % (RTOL, ", ".join("%s %.3g" % kv for kv in WORST.items())))
+    print("largest deviation of the crossed-axes cases, in units of their own bound: %s"
+          % ", ".join("%s %.3g" % kv for kv in WORST_NEW.items()))

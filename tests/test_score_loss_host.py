@@ -1,6 +1,10 @@
 """probaforms_amd.metrics.losses.energy_score_loss / crps_loss without a GPU: the float64 restatement (tests/scoregrad_numpy.py)
-against the energy score's existing restatement (tests/joint_scores_numpy.py) and central differences, the C header against the
-binding, the workspace query, pfm_score_plan and the argument statuses of pfm_score_grad, and the public calls' argument checks.
+against the energy score's existing restatement (tests/joint_scores_numpy.py), central differences and torch-CPU float64 autograd of
+the same formula at the shapes where the GPU test crosses the kernel's axes, the C header against the binding, the workspace query,
+pfm_score_plan and the argument statuses of pfm_score_grad, and the public calls' argument checks.
+
+The autograd yardstick sums the same terms in another order: it is held within scoregrad_numpy.rtol_of(d) of the sum of the
+magnitudes of an output's terms, the bound the GPU test holds the kernel to.
 
 Central differences, step h = 1e-6, on rows whose points lie apart by 0.1 and more: the truncation error h^2 / 6 |f'''| is below
 1e-10 there, and the rounding error of the two values is about 2^-52 |score| / h = 1e-9 for scores of order 1.  The bound is 1e-7.
@@ -68,6 +72,51 @@ def test_restatement_gradient_equals_central_differences(shape, fair):
     # translation invariance: a row's derivatives by its points sum to 0
     total = o["grad_x"].sum(axis=0) + o["grad_y"]
     assert (np.abs(total) <= 1e-13 * (o["mx"].sum(axis=0) + o["my"])).all()
+
+
+def autograd_value_grad(X, Y, fair, budget=1 << 22):
+    """torch-CPU float64 autograd of the rows' scores (a row's outputs depend on that row alone, so the gradient of the sum of the
+    scores is every row's own); the distance is where(d2 > 0, sqrt(.), 0) with the root taken of 1 where d2 = 0, so that a
+    coincident pair adds the subgradient 0; the pairs a block of draws at a time, the blocks' backward passes accumulating
+    -> (scores, spread, grad_x, grad_y)"""
+    A, B = torch.from_numpy(np.array(X, np.float64)).requires_grad_(True), torch.from_numpy(np.array(Y, np.float64)).requires_grad_(True)
+    K, n, d = A.shape
+    D = K - 1 if fair else K
+
+    def dist(diff):
+        d2 = (diff * diff).sum(dim=-1)
+        pos = d2 > 0
+        return torch.where(pos, torch.where(pos, d2, torch.ones_like(d2)).sqrt(), torch.zeros_like(d2))
+
+    t1 = dist(A - B[None]).sum(dim=0) / K
+    t1.sum().backward()
+    spread = torch.zeros(n, dtype=torch.float64)
+    step = max(1, budget // (K * n * d))
+    for k0 in range(0, K, step):
+        part = dist(A[k0:k0 + step, None] - A[None]).sum(dim=(0, 1)) / (2.0 * K * D)
+        (-part.sum()).backward()
+        spread = spread + part.detach()
+    return (t1.detach() - spread).numpy(), spread.numpy(), A.grad.numpy(), B.grad.numpy()
+
+
+AUTOGRAD_CASES = [(1, 3, 2), (2, 3, 1), (33, 7, 17), (257, 3, 2)] + sg.CROSSED + sg.CROSSED_NAN + sg.CROSSED_LAYOUT
+
+
+@pytest.mark.parametrize("fair", (False, True))
+@pytest.mark.parametrize("case", AUTOGRAD_CASES, ids=str)
+def test_restatement_equals_torch_autograd(case, fair):
+    K, n, d = case
+    if K == 1 and fair:
+        return
+    X, Y = sg.rows(K, n, d)
+    o = sg.value_grad(X, Y, fair)
+    scores, spread, gx, gy = autograd_value_grad(X, Y, fair)
+    rtol = sg.rtol_of(d)
+    for name, got, mag in (("scores", scores, "smag"), ("spread", spread, "spread"), ("grad_x", gx, "mx"), ("grad_y", gy, "my")):
+        err, m = np.abs(got - o[name]), np.abs(o[mag])
+        print("%s fair=%s: %s off by at most %.3g of its terms' magnitudes (bound %.3g)"
+              % (case, fair, name, float((err / np.where(m > 0, m, 1.0)).max()), rtol))
+        assert np.isfinite(got).all() and (err <= rtol * m).all(), name
 
 
 def test_restatement_on_hand_made_data():

@@ -1,6 +1,10 @@
 """probaforms_amd.metrics.losses.sinkhorn_loss without a GPU: the float64 restatement's gradient (tests/sinkhorn_grad_numpy.py)
-against central differences of the restatement's own ITERATED value at converged configurations, the C header against the
-binding, the workspace query and the argument statuses of pfm_sinkhorn_grad, and the public call's argument checks.
+against central differences of the restatement's own ITERATED value at converged configurations and against torch-CPU autograd of
+the last step at the shapes where the GPU test crosses the sweep's axes, the C header against the binding, the workspace query and
+the argument statuses of pfm_sinkhorn_grad, and the public call's argument checks.
+
+The autograd yardstick reads the potentials of the restatement's own iteration and differentiates the last step alone, so both
+sides sum the same terms in other orders: the value is held within 1e-12 cmax and a gradient element within 1e-12 M.
 
 At drift <= 1e-13 the envelope-theorem gradient is the derivative of the whole iterated value: central differences with
 h = 1e-5 carry a truncation error of about h^2 |S'''| / 6 ~ 1e-11 and a rounding error of about 1e-16 cmax / h ~ 1e-10, so
@@ -21,6 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import native_libs  # noqa: E402
+import pairgrad_numpy as pg  # noqa: E402
 import sinkhorn_grad_numpy as sg  # noqa: E402
 import sinkhorn_numpy as sn  # noqa: E402
 from probaforms_amd.metrics import _lib, losses  # noqa: E402
@@ -75,6 +80,47 @@ def test_differentiating_through_the_columns_too_doubles_the_gradient(case):
     print("%s: doubled variant off 2 x central differences by at most %.3g, largest element %.3g" % (case, err, np.abs(fd).max()))
     assert err <= 2 * FD_TOL
     assert float(np.abs(twice - fd).max()) >= 0.5 * float(np.abs(fd).max())
+
+
+def autograd_last_step(Xr, Xf, p, eps, old, block=128):
+    """torch-CPU float64 autograd of S = sum_a w_a (fin[0][a] - fin[1][a]), every fin a softmin over the columns of the potentials
+    `old` the last step read, with the columns' coordinates and `old` held fixed: the envelope-theorem gradient the kernel forms.
+    A block of rows at a time, the blocks' backward passes accumulating -> (S, dS/dZ)"""
+    Z = torch.from_numpy(np.concatenate([Xr, Xf])).clone().requires_grad_(True)
+    cols, h = Z.detach(), torch.from_numpy(np.asarray(old))
+    nr, N = len(Xr), Z.shape[0]
+    first = torch.arange(N) < nr
+    w = torch.from_numpy(np.where(np.arange(N) < nr, 1.0 / nr, 1.0 / (N - nr)))          # built in float64
+    total = 0.0
+    for a0 in range(0, N, block):
+        diff = Z[a0:a0 + block, None, :] - cols[None, :, :]
+        d2 = (diff * diff).sum(dim=2)
+        pos = d2 > 0
+        C = torch.where(pos, torch.where(pos, d2, torch.ones_like(d2)).sqrt(), torch.zeros_like(d2)) if p == 1 else d2
+        same = first[a0:a0 + block, None] == first[None, :]
+        minus_inf = torch.full_like(C, -float("inf"))
+        part = 0.0
+        for slot, mask, sign in ((0, ~same, 1.0), (1, same, -1.0)):
+            z = torch.where(mask, (h[slot][None, :] - C) / eps + torch.log(w)[None, :], minus_inf)
+            part = part + sign * (w[a0:a0 + block] * (-eps * torch.logsumexp(z, dim=1))).sum()
+        part.backward()
+        total += float(part.detach())
+    return total, Z.grad.numpy()
+
+
+@pytest.mark.parametrize("p", (1, 2))
+@pytest.mark.parametrize("case", [(65, 63, 17, "plain"), (130, 70, 2, "copies")] + pg.CROSSED, ids=pg.case_id)
+def test_restatement_equals_torch_autograd_of_the_last_step(case, p):
+    Xr, Xf = pg.make(case)
+    eps = float(0.1 * sn.median(Xr, Xf) ** p)
+    cm = sn.cmax(Xr, Xf, p)
+    o = sg.value_drift_grad(Xr, Xf, p, eps, 2)
+    S, grad = autograd_last_step(Xr, Xf, p, eps, o["old"])
+    err = np.abs(grad - o["grad"])
+    print("%s p=%d: cmax / eps %.3g, value off by %.3g cmax, gradient by at most %.3g of M"
+          % (pg.case_id(case), p, cm / eps, abs(S - o["value"]) / cm, float((err / np.where(o["M"] > 0, o["M"], 1.0)).max())))
+    assert np.isfinite(grad).all() and abs(S - o["value"]) <= pg.TOL * cm
+    assert (err <= pg.TOL * o["M"]).all()
 
 
 def test_restatement_on_hand_made_data():

@@ -94,6 +94,24 @@ def test_restatement_equals_torch_autograd_for_equal_sizes(n, p):
     assert (np.abs(grad - o["grad"]) <= 1e-12 * o["M"]).all()
 
 
+@pytest.mark.parametrize("p", (1, 2))
+@pytest.mark.parametrize("case", [(100, 37, 3, 5), (5, 1, 2, 3)] + sl.CROSSED + [s + (None,) for s in sl.CROSSED_AXES], ids=str)
+def test_restatement_equals_torch_autograd_at_the_crossed_shapes(case, p):
+    nr, nf, d, P = case                                           # P None: the coordinate axes
+    Xr, Xf = sl.make(nr, nf, d)
+    theta = None if P is None else sl.unit_directions(P, d)
+    o = sl.value_grad(Xr, Xf, theta, p)
+    A, B = torch.from_numpy(Xr).requires_grad_(True), torch.from_numpy(Xf).requires_grad_(True)
+    L = sl.torch_value(A, B, None if theta is None else torch.from_numpy(theta), p)
+    L.backward()
+    grad = torch.cat([A.grad, B.grad]).numpy()
+    err = np.abs(grad - o["grad"])
+    print("%s p=%d: value off by %.3g Lmag, gradient by at most %.3g M"
+          % (case, p, abs(float(L.detach()) - o["value"]) / o["Lmag"], float((err / np.where(o["M"] > 0, o["M"], 1.0)).max())))
+    assert abs(float(L.detach()) - o["value"]) <= 1e-12 * o["Lmag"]
+    assert (err <= 1e-12 * o["M"]).all()
+
+
 def test_restatement_on_hand_made_data():
     # one real row at 0, one fake row at (3, 4), theta = the axes: W = (3, 4) for p = 1, (9, 16) for p = 2
     o = sl.value_grad(np.zeros((1, 2)), np.array([[3.0, 4.0]]), None, 1)
