@@ -70,6 +70,81 @@ def assert_pattern_independent(outs, what):
                                                                     int(torch.isnan(t.double()).sum())))
 
 
+GUARD_BYTE = 0xC3
+GUARD_FRONT = 4096
+GUARD_BACK_MAX = 1 << 20
+GUARD_ALIGN = 256             # the libraries lay sub-buffers out with align256
+
+
+class Guarded:
+    """`nbytes` interior bytes (at least 16) at a 256-byte-aligned address inside one larger allocation, GUARD_FRONT guard bytes in
+    front and max(4096, min(nbytes, 1 MiB)) behind (an extra workgroup's whole record still lands there); guards hold GUARD_BYTE,
+    the interior `fill`.  What a call writes outside the interior is seen by assert_guards_intact, what it writes inside by
+    written() / high_water()."""
+
+    def __init__(self, nbytes, fill, device="cuda"):
+        if fill not in (_FILL["ones"], _FILL["huge"]):
+            raise ValueError("guarded(): fill is 0xFF or 0x7F (the `ones` / `huge` bytes of PATTERNS), not %r" % (fill,))
+        self.fill = int(fill)
+        self.nbytes = max(int(nbytes), 16)
+        self.back = max(4096, min(int(nbytes), GUARD_BACK_MAX))
+        self._raw = torch.full((GUARD_FRONT + GUARD_ALIGN - 1 + self.nbytes + self.back,), GUARD_BYTE, dtype=torch.uint8, device=device)
+        self._start = GUARD_FRONT + (-(self._raw.data_ptr() + GUARD_FRONT)) % GUARD_ALIGN
+        self.view = self._raw[self._start:self._start + self.nbytes]
+        self.view.fill_(self.fill)
+
+    def typed(self, dtype, shape):
+        """the interior's bytes as an output tensor of `dtype` and `shape`, which must take exactly the bytes asked for; an output of
+        fewer than the 16 bytes `view` has at least gives the rest of them to the back guard, so the guard starts where the output ends"""
+        want = torch.empty((), dtype=dtype).element_size()
+        for s in shape:
+            want *= int(s)
+        assert want == self.nbytes or 0 < want < self.nbytes == 16, "typed(): %r of %s is not the %d guarded bytes" % (tuple(shape), dtype, self.nbytes)
+        if want < self.nbytes:
+            self.retract(self.nbytes - want)
+        return self.view.view(dtype).view(*shape)
+
+    def retract(self, nbytes):
+        """tell the handle that the interior ends `nbytes` earlier than it does: those bytes become guard (the detector's self-test;
+        a `view` taken before still spans them)"""
+        assert 0 < nbytes < self.nbytes
+        self.nbytes -= int(nbytes)
+        self.back += int(nbytes)
+        self._raw[self._start + self.nbytes:self._start + self.nbytes + int(nbytes)] = GUARD_BYTE
+        self.view = self._raw[self._start:self._start + self.nbytes]
+
+    def assert_guards_intact(self, what):
+        end = self._start + self.nbytes
+        for name, region, origin in (("behind", self._raw[end:], 0), ("in front of", self._raw[:self._start], -self._start)):
+            bad = region != GUARD_BYTE
+            if bool(bad.any()):
+                at = bad.nonzero().flatten()
+                raise AssertionError("%s: wrote %s its %d bytes: %d guard bytes changed, the first at %s%+d, the last at %s%+d"
+                                     % (what, name, self.nbytes, at.numel(), "end" if origin == 0 else "start", int(at[0]) + origin,
+                                        "end" if origin == 0 else "start", int(at[-1]) + origin))
+
+    def written(self):
+        """bool mask over the interior: the bytes that differ from `fill`"""
+        return self.view != self.fill
+
+
+def guarded(nbytes, fill, device="cuda"):
+    return Guarded(nbytes, fill, device)
+
+
+def high_water(h1, h2):
+    """the offset after the last interior byte written in either of two runs of the same call on the two fills (a byte that one run
+    happens to set to its own fill value is seen in the other); 0: nothing written"""
+    assert h1.nbytes == h2.nbytes and h1.fill != h2.fill
+    step = 1 << 24                                    # from the end, a piece at a time: a workspace can be a gigabyte
+    for hi in range(h1.nbytes, 0, -step):
+        lo = max(0, hi - step)
+        at = ((h1.view[lo:hi] != h1.fill) | (h2.view[lo:hi] != h2.fill)).nonzero().flatten()
+        if at.numel():
+            return lo + int(at[-1]) + 1
+    return 0
+
+
 def assert_all_written(outs, what, allow=()):
     for name, t in outs.items():
         if name in allow:
