@@ -82,7 +82,10 @@ size_t pfp_workspace_bytes(const rnvp_shape *shape, int64_t k_cnt);
  *   state   [n_rows, d] x PFP_STATE_BYTES   (nullable) read, updated with this call's draws, written back
  *   x_out   [k_cnt, n_rows, d]        (nullable) the draws
  *   xt_out  [n_rows, d, k_total]      (nullable) the draws transposed, written at columns k_lo .. k_lo + k_cnt
- * Exactly one of seeds / z is given.  On either path row_offset + n_rows <= n_total (the rows of the whole job) and
+ * Exactly one of seeds / z is given.  With seeds the call is the one exception to "returns without synchronising": the HOST array
+ * is copied into the workspace by a stream-ordered host-to-device copy (hipMemcpyAsync), so it must stay alive until `stream`
+ * has passed the call; from pageable memory that copy may make the call wait for the work enqueued on `stream` before it, and a
+ * capture would record the host address, not the values.  Given z the call enqueues one launch and nothing else.  On either path row_offset + n_rows <= n_total (the rows of the whole job) and
  * k_lo + k_cnt <= k_total, whichever outputs are asked for (PFP_EINVAL otherwise).  PFP_EUNSUPPORTED when the shape's per-tile image exceeds a CU's LDS.
  */
 int pfp_draw_accumulate(void *stream, const rnvp_shape *shape, const float *params, const uint8_t *masks,
