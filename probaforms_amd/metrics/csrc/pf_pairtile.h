@@ -4,9 +4,11 @@
 // thread (ti, tj) = (tid >> 4, tid & 15) owns the 4 x 4 pairs of rows ti + 16 a and columns tj + 16 b.  The two row sets are
 // staged through LDS in chunks of DC features, and d^2 is accumulated as fma(df, df, acc) over the features in order, in
 // float64 (chunk_d2).  No square root is taken and no norm / dot-product identity is used.  Every kernel that needs a
-// distance gets it from chunk_d2: pf_knn.hip, pf_nn.hip, pf_energy.hip and pf_perm.hip through tile_d2, pf_metrics.hip through its
-// tile_d2_pooled, which differs in how it stages only.  So across kernels a duplicated row is at distance exactly 0,
-// `d^2 < radius^2` compares values of one formula, and a statistic recomputed by another entry point has the same bits.
+// distance gets it from chunk_d2: pf_knn.hip, pf_nn.hip, pf_energy.hip, pf_perm.hip, pf_sinkhorn.hip and the row-gradient sweep of
+// pf_gradsweep.h through tile_d2, pf_metrics.hip through its tile_d2_pooled, which differs in how it stages only.  So across
+// kernels a duplicated row is at distance exactly 0, `d^2 < radius^2` compares values of one formula, and a statistic recomputed
+// by another entry point has the same bits.  Only the distance and the tiles live here; how a sweep's column tiles are shared out
+// over workgroups (Slices) is pf_gradsweep.h's.
 #ifndef PF_PAIRTILE_H
 #define PF_PAIRTILE_H
 
@@ -122,42 +124,6 @@ __device__ inline void tile_d2(const SrcA &A, int64_t I0, const SrcB &B, int64_t
         __syncthreads();
         chunk_d2(sA, sB, dc, acc);
     }
-}
-
-// ---- column slices ---------------------------------------------------------------------------------------
-// The row-gradient sweeps (pf_pairgrad.hip, pf_sinkgrad.hip) give a workgroup a row block of the pooled sample, a slice of the
-// column tiles and a chunk of DC features; a finish kernel sums the slices' partials [slices, n, d] in index order.
-
-struct Slices {             // how the column tiles of a row block are shared out; a function of (n, d) only
-    int64_t nb;             // tiles per side
-    int64_t fc;             // feature chunks of the gradient
-    int64_t per;            // column tiles per slice
-    int64_t count;          // slices
-};
-
-constexpr int64_t TARGET_WORKGROUPS = 1024;    // about four per CU of the device the library is written for
-
-__host__ inline Slices slices_of(int64_t n, int64_t d) {
-    Slices s;
-    s.nb = tiles_per_side(n);
-    s.fc = (d + DC - 1) / DC;
-    int64_t want = (TARGET_WORKGROUPS + s.nb * s.fc - 1) / (s.nb * s.fc);
-    if (want < 1) want = 1;
-    if (want > s.nb) want = s.nb;
-    s.per = (s.nb + want - 1) / want;
-    s.count = (s.nb + s.per - 1) / s.per;
-    return s;
-}
-
-// the sizes such a sweep and its finish accept: n pooled rows of d features, the first n_first of the first sample
-inline bool pair_args_ok(int64_t n, int64_t d, int64_t n_first) {
-    if (n < 2 || n > (int64_t)INT32_MAX || d < 1 || d > 65535 * (int64_t)DC) return false;      // feature chunks are grid.z
-    if (n_first < 1 || n_first >= n) return false;
-    const Slices sl = slices_of(n, d);
-    if (sl.count > 65535) return false;                                                           // slices are grid.y
-    if (d > INT64_MAX / n / sl.count / (int64_t)sizeof(double) / 2) return false;                 // the partials' bytes overflow
-    if ((n * d + NT - 1) / NT + 1 > (int64_t)INT32_MAX) return false;                             // the finish's grid.x
-    return true;
 }
 
 }  // namespace

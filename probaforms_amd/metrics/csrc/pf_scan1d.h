@@ -1,6 +1,8 @@
 // pf_scan1d.h -- what the per-column bootstrap kernels of libpf_metrics.so share (pf_metrics1d.hip, pf_wasserstein.hip): the
 // draw counts of a replicate, a column's sorted order with its tie groups, and the workgroup's integer scan and fixed-order sum.
-// The draw counts (launch_counts) also serve pf_energy.hip and pf_sinkhorn.hip, whose size check pair_sizes_ok is.
+// The draw counts (launch_counts) also serve pf_energy.hip and pf_sinkhorn.hip, whose size check pair_sizes_ok is; the fixed-order
+// sum and maximum (block_sum, block_max) serve every finish kernel that reduces one value per thread, and the two Sinkhorn
+// finishes share their tail here (sinkhorn_value_drift).
 #ifndef PF_SCAN1D_H
 #define PF_SCAN1D_H
 
@@ -97,6 +99,38 @@ __device__ double block_sum(double v, double *sd) {
     const double s = sd[0];
     __syncthreads();
     return s;
+}
+
+// the same tree with fmax
+__device__ double block_max(double v, double *sd) {
+    const int tid = threadIdx.x;
+    sd[tid] = v;
+    __syncthreads();
+    for (int off = NT / 2; off > 0; off >>= 1) {
+        if (tid < off) sd[tid] = fmax(sd[tid], sd[tid + off]);
+        __syncthreads();
+    }
+    const double s = sd[0];
+    __syncthreads();
+    return s;
+}
+
+// the tail of the two Sinkhorn finishes (pf_sinkhorn.hip, pf_sinkgrad.hip) for the four potentials of n pooled rows under one
+// weighting: value = sum_i weight(i) (fin[0][i] - fin[1][i]), thread t taking i = t, t + NT, .. and then block_sum;
+// drift = the largest |cur - prev| of a potential (0 without has_prev).  A row of weight 0 takes no part in either.
+template <class Weight>
+__device__ void sinkhorn_value_drift(const double *fin, const double *cur, const double *prev, int has_prev, int64_t n,
+                                     Weight weight, double *sd, double &value, double &drift) {
+    double v = 0.0, dr = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += NT) {
+        const double w = weight(i);
+        if (w > 0.0) {
+            v = v + w * (fin[i] - fin[n + i]);
+            if (has_prev) dr = fmax(dr, fmax(fabs(cur[i] - prev[i]), fabs(cur[n + i] - prev[n + i])));
+        }
+    }
+    value = block_sum(v, sd);
+    drift = block_max(dr, sd);
 }
 
 }  // namespace

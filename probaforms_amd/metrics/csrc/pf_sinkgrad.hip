@@ -18,12 +18,13 @@
 //                      added once, and the softmin is averaged with the old potential (or, in the last step, stored as it is)
 //                      into the other buffer.  Columns past the end carry h = -inf and add exp(-inf) = 0; a wave whose 16
 //                      columns are such alone skips the tile.
-//   k_sinkhorn_sweep   workgroup (I, s, fc) owns the 64 rows a of row block I of the pooled sample, the column tiles of slice s
-//                      and the features 16 fc .. 16 fc + 15 (k_pair_sweep's structure): one exp per pair gives sgn P c_p, and
-//                      sum_b coef_ab (z_a[k] - z_b[k]) is kept in registers across the slice, summed over a row's 16 lanes (xor
-//                      tree) and written to partial[s, a, k].
+//   k_sinkhorn_sweep   workgroup (I, s, fc) runs row_grad_sweep of pf_gradsweep.h over its row block of the pooled sample, column
+//                      slice and feature chunk with coef_ab = sgn P c_p, one exp per pair.
 //   k_sinkhorn_grad_finish  grad[a, k] = w_a (the slices' partials in index order); its last workgroup forms value and drift as
-//                      k_sinkhorn_finish does and copies the potentials out.
+//                      k_sinkhorn_finish does (sinkhorn_value_drift of pf_scan1d.h) and copies the potentials out.
+// k_sinkhorn_step1 is NOT k_sinkhorn_step of pf_sinkhorn.hip with one replicate: that kernel shares the replicates out over the
+// waves, this one the columns of a tile, and the one-replicate form measured 1.5 to 2.1 times faster for it
+// (profiles/r23_sinkhorn_loss_time.txt).  The two are kept apart on purpose.
 // A row's softmin is folded per wave over the columns in index order and the waves are merged in wave order; the slices depend
 // on (n, d) only: the order of every sum depends on (n, n_first, d) only, and two calls give the same bytes.  No float atomics.
 #include <hip/hip_runtime.h>
@@ -32,7 +33,7 @@
 #include <stdint.h>
 
 #include "pf_metrics.h"
-#include "pf_pairtile.h"
+#include "pf_gradsweep.h"
 #include "pf_scan1d.h"
 
 namespace {
@@ -115,114 +116,55 @@ __global__ void __launch_bounds__(NT) k_sinkhorn_step1(const double *Z, int64_t 
     }
 }
 
+// row_grad_sweep's Coef: coef_ab = sgn P c_p(d^2) from the rows' final potentials and the columns' old ones
+struct SinkCoef {
+    int64_t n, n_first;
+    int p;
+    double inv_eps, lw_first, lw_second;
+    const double *__restrict__ old;
+    double fa[4][2];                                       // the rows' final potentials / eps: cross, self
+    double ob[4][2];                                       // the columns' old potentials / eps - log n: in flight under tile_d2
+    __device__ __forceinline__ void rows(const double *__restrict__ fin) {
+        const int64_t r0 = (int64_t)blockIdx.x * TILE + (threadIdx.x >> 4);
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            const int64_t r = r0 + 16 * a;
+            fa[a][0] = r < n ? fin[r] * inv_eps : 0.0;
+            fa[a][1] = r < n ? fin[n + r] * inv_eps : 0.0;
+        }
+    }
+    __device__ __forceinline__ void columns(int64_t J0) {
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const int64_t cb = J0 + (threadIdx.x & 15) + 16 * b;
+            const double lw = cb < n_first ? lw_first : lw_second;
+            ob[b][0] = cb < n ? fma(old[cb], inv_eps, lw) : 0.0;
+            ob[b][1] = cb < n ? fma(old[n + cb], inv_eps, lw) : 0.0;
+        }
+    }
+    __device__ __forceinline__ double pair(int a, int b, double d2, bool row_first, bool col_first, bool ok) const {
+        const bool same = row_first == col_first;
+        const double C = p == 1 ? sqrt(d2) : d2;
+        const double e = exp((same ? fa[a][1] + ob[b][1] : fa[a][0] + ob[b][0]) - C * inv_eps);
+        const double c = p == 1 ? (d2 == 0.0 ? 0.0 : 1.0 / C) : 2.0;
+        return ok ? (same ? -e : e) * c : 0.0;
+    }
+};
+
 // GF: the features of a gradient chunk that get registers (4 for d <= 4, else DC), as k_pair_sweep's; the 4 x 16 float64
 // accumulators beside the exp run one wave per SIMD
 template <int GF>
 __global__ void __launch_bounds__(NT, GF == DC ? 1 : 2)
     k_sinkhorn_sweep(const double *Z, int64_t n, int64_t d, int64_t n_first, int p, double inv_eps,
                      const double *__restrict__ fin, const double *__restrict__ old, Slices sl, double *partial) {
-    __shared__ double sA[DC][TPAD], sB[DC][TPAD];          // the chunks tile_d2 walks
-    __shared__ double xA[DC][TPAD], xB[DC][TPAD];          // d > DC: the gradient's chunk of the rows and of the column tile
-    const int tid = threadIdx.x, ti = tid >> 4, tj = tid & 15;
-    const int64_t I0 = (int64_t)blockIdx.x * TILE;
-    const int64_t s = blockIdx.y;
-    const int64_t k0 = (int64_t)blockIdx.z * DC;           // first feature of this workgroup's gradient chunk
-    const int dcg = (int)((d - k0) < DC ? (d - k0) : DC);
-    const bool resident = d <= DC;
-    const Plain pooled = {Z, n, d};
-    const double lw_first = -log((double)n_first), lw_second = -log((double)(n - n_first));
-
-    int64_t J = s * sl.per, J_end = J + sl.per;
-    if (J_end > sl.nb) J_end = sl.nb;
-
-    double (*gA)[TPAD] = resident ? sA : xA;
-    double (*gB)[TPAD] = resident ? sB : xB;
-    if (resident) stage(pooled, I0, 0, (int)d, sA);        // visible after tile_d2's first barrier
-    else stage(pooled, I0, k0, dcg, xA);
-
-    // row ti + 16 a of the block exists while 16 a < rows_left and is of the first sample while 16 a < first_left
-    const int rows_left = (int)(n - I0 - ti < TILE ? n - I0 - ti : TILE);
-    const int first_left = (int)(n_first - I0 - ti < TILE ? (n_first - I0 - ti > -TILE ? n_first - I0 - ti : -TILE) : TILE);
-
-    double fa[4][2];                                       // the rows' final potentials / eps: cross, self
-    double G[4][GF];
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-        const int64_t r = I0 + ti + 16 * a;
-        fa[a][0] = r < n ? fin[r] * inv_eps : 0.0;
-        fa[a][1] = r < n ? fin[n + r] * inv_eps : 0.0;
-#pragma unroll
-        for (int k = 0; k < GF; ++k) G[a][k] = 0.0;
-    }
-
-    for (; J < J_end; ++J) {
-        const int64_t J0 = J * TILE;
-        double ob[4][2];                                   // the columns' old potentials / eps - log n: in flight under tile_d2
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const int64_t cb = J0 + tj + 16 * b;
-            const double lw = cb < n_first ? lw_first : lw_second;
-            ob[b][0] = cb < n ? fma(old[cb], inv_eps, lw) : 0.0;
-            ob[b][1] = cb < n ? fma(old[n + cb], inv_eps, lw) : 0.0;
-        }
-        if (!resident) {
-            __syncthreads();                               // the previous tile's reads of xB are done
-            stage(pooled, J0, k0, dcg, xB);
-        }
-        double dd[4][4];
-        tile_d2(pooled, I0, pooled, J0, resident, sA, sB, dd);
-
-        // ---- dd <- sgn P c_p(d^2) ----
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-            const int64_t cb = J0 + tj + 16 * b;
-            const bool col_ok = cb < n, col_first = cb < n_first;
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                const bool same = (16 * a < first_left) == col_first;
-                const double d2 = dd[a][b];
-                const double C = p == 1 ? sqrt(d2) : d2;
-                const double e = exp((same ? fa[a][1] + ob[b][1] : fa[a][0] + ob[b][0]) - C * inv_eps);
-                const double c = p == 1 ? (d2 == 0.0 ? 0.0 : 1.0 / C) : 2.0;
-                dd[a][b] = col_ok && 16 * a < rows_left ? (same ? -e : e) * c : 0.0;
-            }
-        }
-
-        // ---- the differences, feature by feature ----
-#pragma unroll
-        for (int k = 0; k < GF; ++k)
-            if (k < dcg) {                                 // (uniform)
-                double xa[4], yb[4];
-#pragma unroll
-                for (int a = 0; a < 4; ++a) xa[a] = gA[k][ti + 16 * a];
-#pragma unroll
-                for (int b = 0; b < 4; ++b) yb[b] = gB[k][tj + 16 * b];
-#pragma unroll
-                for (int a = 0; a < 4; ++a)
-#pragma unroll
-                    for (int b = 0; b < 4; ++b) G[a][k] = fma(dd[a][b], xa[a] - yb[b], G[a][k]);
-            }
-    }
-
-    // ---- a row's 16 lanes: xor tree; lane tj then writes feature tj ----
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-        double out = 0.0;
-#pragma unroll
-        for (int k = 0; k < GF; ++k) {
-            double v = G[a][k];
-#pragma unroll
-            for (int m = 1; m < 16; m <<= 1) v = v + __shfl_xor(v, m, 16);
-            if (tj == k) out = v;
-        }
-        const int64_t r = I0 + ti + 16 * a;
-        if (r < n && tj < dcg) partial[(s * n + r) * d + k0 + tj] = out;
-    }
+    SinkCoef coef = {n, n_first, p, inv_eps, -log((double)n_first), -log((double)(n - n_first)), old};
+    coef.rows(fin);
+    row_grad_sweep<true, GF>(Z, n, d, n_first, sl, coef, partial);
 }
 
-// grad[a, k] = w_a sum_s partial[s, a, k], element e = a d + k of workgroups 0 .. gridDim.x - 2 (there are none for the value
-// alone); the last workgroup: value = sum_i w_i (fin[0][i] - fin[1][i]), a strided sum per thread and a tree over the threads,
-// drift = the largest |cur - prev| of a potential (the last averaged step's change), and the potentials, fin then cur
+// grad[a, k] = w_a sum_s partial[s, a, k] (finish_rows; there are no such workgroups for the value alone); the last workgroup:
+// value = sum_i w_i (fin[0][i] - fin[1][i]) and drift = the largest |cur - prev| of a potential (the last averaged step's
+// change), and the potentials, fin then cur
 __global__ void __launch_bounds__(NT) k_sinkhorn_grad_finish(const double *partial, int64_t n, int64_t d, int64_t n_first,
                                                              int64_t slices, const double *__restrict__ fin,
                                                              const double *__restrict__ cur, const double *__restrict__ prev,
@@ -232,31 +174,16 @@ __global__ void __launch_bounds__(NT) k_sinkhorn_grad_finish(const double *parti
     __shared__ double sd[NT];
     const int tid = threadIdx.x;
     const double w_first = 1.0 / (double)n_first, w_second = 1.0 / (double)(n - n_first);
+    const auto weight = [=](int64_t i) { return i < n_first ? w_first : w_second; };
     if (blockIdx.x + 1 < gridDim.x) {
-        const int64_t e = (int64_t)blockIdx.x * NT + tid;
-        if (e < n * d) {
-            const int64_t a = e / d;
-            double v = partial[e];
-            for (int64_t s = 1; s < slices; ++s) v = v + partial[s * n * d + e];
-            grad[e] = (a < n_first ? w_first : w_second) * v;
-        }
+        finish_rows(partial, n, d, slices, weight, grad);
         return;
     }
-    double v = 0.0, dr = 0.0;
-    for (int64_t i = tid; i < n; i += NT) {
-        v = v + (i < n_first ? w_first : w_second) * (fin[i] - fin[n + i]);
-        if (has_prev) dr = fmax(dr, fmax(fabs(cur[i] - prev[i]), fabs(cur[n + i] - prev[n + i])));
-    }
-    const double total = block_sum(v, sd);
-    sd[tid] = dr;
-    __syncthreads();
-    for (int off = NT / 2; off > 0; off >>= 1) {
-        if (tid < off) sd[tid] = fmax(sd[tid], sd[tid + off]);
-        __syncthreads();
-    }
+    double total, dr;
+    sinkhorn_value_drift(fin, cur, prev, has_prev, n, weight, sd, total, dr);
     if (tid == 0) {
         value[0] = total;
-        drift[0] = sd[0];
+        drift[0] = dr;
     }
     if (potentials)
         for (int64_t i = tid; i < 2 * n; i += NT) {
@@ -273,7 +200,7 @@ Layout layout_of(int64_t n, int64_t d) {
     const Slices sl = slices_of(n, d);
     Layout l;
     l.pot = align256(sizeof(double) * 2 * (size_t)n);
-    l.partial = align256(sizeof(double) * (size_t)(sl.count * n * d));
+    l.partial = partial_bytes(sl, n, d);
     l.total = 3 * l.pot + l.partial;
     return l;
 }

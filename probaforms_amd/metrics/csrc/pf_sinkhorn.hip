@@ -20,7 +20,8 @@
 //                    last tile of a sample the softmin -eps (max + log sum) is averaged with the old potential (or, in the
 //                    last step, stored as it is) into the other buffer: potentials ping-pong, every step reads old values only.
 //   k_sinkhorn_finish  value = sum_i w_i (pot[0][i] - pot[1][i]) over the rows of non-zero count, a strided sum per thread and
-//                    a tree over the threads; drift = the largest |change| of such a row's potentials in the last averaged step.
+//                    a tree over the threads; drift = the largest |change| of such a row's potentials in the last averaged step
+//                    (sinkhorn_value_drift of pf_scan1d.h, which pf_sinkgrad.hip's finish uses with the weights 1 / n).
 // A (row, replicate) pair is folded by one thread over the columns in index order: the order of every sum depends on
 // (nr, nf, d) only, and a replicate's value, drift and potentials are bitwise the same alone, in any group, in any call.  A
 // column of count 0 (or past the end of its sample) carries hl = -inf and adds exp(-inf) = 0; a tile of such columns alone is
@@ -158,26 +159,15 @@ __global__ void __launch_bounds__(NT) k_sinkhorn_finish(const int32_t *__restric
     const int tid = threadIdx.x;
     const int64_t rep = blockIdx.x, N = nr + nf;
     const int32_t *c = cnt + rep * N;
-    const double *f = fin + rep * 2 * N, *a = cur + rep * 2 * N, *b = prev + rep * 2 * N;
-    double v = 0.0, dr = 0.0;
-    for (int64_t i = tid; i < N; i += NT) {
+    const double *f = fin + rep * 2 * N;
+    double total, dr;
+    sinkhorn_value_drift(f, cur + rep * 2 * N, prev + rep * 2 * N, has_prev, N, [=](int64_t i) {
         const int32_t ci = c[i];
-        if (ci > 0) {
-            const double wgt = (double)ci / (double)(i < nr ? nr : nf);
-            v = v + wgt * (f[i] - f[N + i]);
-            if (has_prev) dr = fmax(dr, fmax(fabs(a[i] - b[i]), fabs(a[N + i] - b[N + i])));
-        }
-    }
-    const double total = block_sum(v, sd);
-    sd[tid] = dr;
-    __syncthreads();
-    for (int off = NT / 2; off > 0; off >>= 1) {
-        if (tid < off) sd[tid] = fmax(sd[tid], sd[tid + off]);
-        __syncthreads();
-    }
+        return ci > 0 ? (double)ci / (double)(i < nr ? nr : nf) : 0.0;
+    }, sd, total, dr);
     if (tid == 0) {
         value[rep] = total;
-        drift[rep] = sd[0];
+        drift[rep] = dr;
     }
     if (potentials)
         for (int64_t i = tid; i < 2 * N; i += NT) potentials[rep * 2 * N + i] = f[i];

@@ -16,7 +16,7 @@
 //   k_slice_given    the caller's order instead (perm_in): the projections of the rows in that order, any n.
 //   k_slice_couple   one thread per sorted real element and one per sorted fake element; each walks its own range of partners in
 //                    ascending order, so it writes the derivative by its row's projection exactly once, through the permutation.
-//                    The real side also adds the value's terms; a workgroup's are summed in the fixed LDS tree.
+//                    The real side also adds the value's terms; a workgroup's are summed by block_sum (pf_scan1d.h).
 //   k_slice_finish   rows[a, :] = (1 / P) sum_k g_k[a] theta_k with k ascending, and the value from the workgroups' partials.
 // No float atomics; every sum's order depends on (nr, nf, P) only and every workspace byte read was written by the same call, so
 // the outputs are bitwise the same in any call.  The projection is k_project's: the sum starts at 0 and runs over the features in
@@ -29,6 +29,7 @@
 
 #include "pf_common.h"
 #include "pf_metrics.h"
+#include "pf_scan1d.h"
 
 namespace {
 
@@ -46,17 +47,6 @@ __device__ inline double project_row(const double *z, const double *th, int64_t 
         acc = acc + prod;
     }
     return acc;
-}
-
-__device__ inline double tree_sum(double v, double *sd) {
-    const int tid = threadIdx.x;
-    sd[tid] = v;
-    __syncthreads();
-    for (int off = NT / 2; off > 0; off >>= 1) {
-        if (tid < off) sd[tid] = sd[tid] + sd[tid + off];
-        __syncthreads();
-    }
-    return sd[0];
 }
 
 // the sort route's projections, unsorted, into vals [P, N] (and cols_out): a workgroup takes NT pooled rows and KC directions.  The
@@ -220,7 +210,7 @@ __global__ void __launch_bounds__(NT) k_slice_couple(const double *__restrict__ 
         }
         if (!real) val = 0.0;                                            // every pair's value term is the real side's
     }
-    const double s = tree_sum(val, sd);
+    const double s = block_sum(val, sd);
     if (threadIdx.x == 0) partial[k * gridDim.x + blockIdx.x] = s;
 }
 
@@ -249,7 +239,7 @@ __global__ void __launch_bounds__(NT) k_slice_finish(const double *__restrict__ 
     }
     double v = 0.0;
     for (int64_t i = tid; i < n_partial; i += NT) v = v + partial[i];
-    const double total = tree_sum(v, sd);
+    const double total = block_sum(v, sd);
     if (tid == 0) value[0] = total * inv_cells / (double)P;
 }
 

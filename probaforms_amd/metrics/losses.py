@@ -53,67 +53,54 @@ MAX_PROJECTIONS = 65535                  # pfm_slice_grad's n_proj: the directio
 _MAX_LDS_ROWS = _lib.SLICE_LDS_ROWS      # rows per sample up to which pfm_slice_grad sorts itself; above, torch.sort and perm_in
 
 
-class PairLossFunction(torch.autograd.Function):
-    """L = sum_ab w[a] w[b] g(d2(a, b)) of the pooled rows [Xr; Xf] as one autograd node.
+class PooledLossFunction(torch.autograd.Function):
+    """A scalar loss of the pooled rows Z = [Xr; Xf] as one autograd node: the node of energy_loss / mmd_loss (pfm_pair_grad),
+    sinkhorn_loss (pfm_sinkhorn_grad) and sliced_wasserstein_loss / wasserstein_1d_loss (pfm_slice_grad).
 
-    forward : pfm_pair_grad once: the value and, if an input requires a gradient, dL/dZ [N, d], which is kept
+    call(Z, nr, want_rows) runs the loss's entry point once and returns (value 0-d, rows = dL/dZ [N, d] or None, further 0-d
+    outputs ...): _pair_call, _sinkhorn_call or _slice_call with the loss's constants bound.
+    forward : the call; rows is kept if an input requires a gradient; -> (value, further outputs ...), the further ones (the
+              Sinkhorn drift) marked non-differentiable
     backward: dL/dZ times the incoming scalar, split into the real and the fake rows"""
 
     @staticmethod
-    def forward(ctx, kind, gammas, Xr, Xf):
-        nr = Xr.shape[0]
-        want = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
+    def forward(ctx, call, Xr, Xf):
+        ctx.nr = Xr.shape[0]
+        want = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
         Z = torch.cat([Xr.detach(), Xf.detach()], dim=0).contiguous()
-        N, d = Z.shape
-        value = torch.empty((), dtype=torch.float64, device=Z.device)
-        rows = torch.empty_like(Z) if want else None
-        ws = torch.empty(_lib.pair_grad_workspace_bytes(N, d, nr), dtype=torch.uint8, device=Z.device)
-        _lib.pair_grad(kind, gammas, Z, nr, value, rows, ws)
-        ctx.nr = nr
+        value, rows, *more = call(Z, ctx.nr, want)
+        ctx.mark_non_differentiable(*more)
         if want:
             ctx.save_for_backward(rows)
-        return value
+        return (value, *more)
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, gL):
+    def backward(ctx, gL, *_):
         (rows,) = ctx.saved_tensors
         G = rows * gL
-        return (None, None, G[:ctx.nr] if ctx.needs_input_grad[2] else None,
-                G[ctx.nr:] if ctx.needs_input_grad[3] else None)
+        return None, G[:ctx.nr] if ctx.needs_input_grad[1] else None, G[ctx.nr:] if ctx.needs_input_grad[2] else None
 
 
-class SinkhornLossFunction(torch.autograd.Function):
-    """The debiased Sinkhorn divergence of the pooled rows [Xr; Xf] (uniform weights) as one autograd node.
+def _outputs(Z, want_rows, workspace_bytes):
+    """what every pooled entry point fills: (value 0-d, rows [N, d] or None, the workspace)"""
+    return (torch.empty((), dtype=torch.float64, device=Z.device), torch.empty_like(Z) if want_rows else None,
+            torch.empty(workspace_bytes, dtype=torch.uint8, device=Z.device))
 
-    forward : pfm_sinkhorn_grad once: value, drift and, if an input requires a gradient, the envelope-theorem dS/dZ [N, d],
-              which is kept; drift is marked non-differentiable
-    backward: dS/dZ times the incoming scalar, split into the real and the fake rows"""
 
-    @staticmethod
-    def forward(ctx, p, eps, n_sinkhorn, Xr, Xf):
-        nr = Xr.shape[0]
-        want = ctx.needs_input_grad[3] or ctx.needs_input_grad[4]
-        Z = torch.cat([Xr.detach(), Xf.detach()], dim=0).contiguous()
-        N, d = Z.shape
-        value = torch.empty((), dtype=torch.float64, device=Z.device)
-        drift = torch.empty((), dtype=torch.float64, device=Z.device)
-        rows = torch.empty_like(Z) if want else None
-        ws = torch.empty(_lib.sinkhorn_grad_workspace_bytes(N, d, nr), dtype=torch.uint8, device=Z.device)
-        _lib.sinkhorn_grad(Z, nr, p, eps, n_sinkhorn, value, drift, rows, None, ws)
-        ctx.nr = nr
-        ctx.mark_non_differentiable(drift)
-        if want:
-            ctx.save_for_backward(rows)
-        return value, drift
+def _pair_call(kind, gammas, Z, nr, want_rows):
+    """pfm_pair_grad once on the pooled rows Z [N, d] (float64, contiguous, on the device): -> (value 0-d, rows [N, d] or None)"""
+    value, rows, ws = _outputs(Z, want_rows, _lib.pair_grad_workspace_bytes(Z.shape[0], Z.shape[1], nr))
+    _lib.pair_grad(kind, gammas, Z, nr, value, rows, ws)
+    return value, rows
 
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gS, _gdrift):
-        (rows,) = ctx.saved_tensors
-        G = rows * gS
-        return (None, None, None, G[:ctx.nr] if ctx.needs_input_grad[3] else None,
-                G[ctx.nr:] if ctx.needs_input_grad[4] else None)
+
+def _sinkhorn_call(p, eps, n_sinkhorn, Z, nr, want_rows):
+    """pfm_sinkhorn_grad once, as _pair_call: -> (value 0-d, the envelope-theorem rows [N, d] or None, drift 0-d)"""
+    value, rows, ws = _outputs(Z, want_rows, _lib.sinkhorn_grad_workspace_bytes(Z.shape[0], Z.shape[1], nr))
+    drift = torch.empty_like(value)
+    _lib.sinkhorn_grad(Z, nr, p, eps, n_sinkhorn, value, drift, rows, None, ws)
+    return value, rows, drift
 
 
 def _given_order(Z, nr, theta):
@@ -130,43 +117,14 @@ def _given_order(Z, nr, theta):
 
 
 def _slice_call(p, Z, nr, theta, want_rows, cols_out=None, perm_out=None):
-    """pfm_slice_grad once on the pooled rows Z [N, d] (float64, contiguous, on the device): -> (value 0-d, rows [N, d] or None).
-    theta [P, d] on the device or None (the coordinate axes).  A sample above _MAX_LDS_ROWS is ordered by torch.sort"""
+    """pfm_slice_grad once, as _pair_call: -> (value 0-d, rows [N, d] or None).  theta [P, d] on the device or None (the
+    coordinate axes), a constant.  A sample above _MAX_LDS_ROWS is ordered by torch.sort"""
     N, d = Z.shape
     P = d if theta is None else theta.shape[0]
     perm_in = _given_order(Z, nr, theta) if max(nr, N - nr) > _MAX_LDS_ROWS else None
-    value = torch.empty((), dtype=torch.float64, device=Z.device)
-    rows = torch.empty_like(Z) if want_rows else None
-    ws = torch.empty(_lib.slice_grad_workspace_bytes(N, d, nr, P), dtype=torch.uint8, device=Z.device)
+    value, rows, ws = _outputs(Z, want_rows, _lib.slice_grad_workspace_bytes(N, d, nr, P))
     _lib.slice_grad(p, Z, nr, theta, P, perm_in, value, rows, cols_out, perm_out, ws)
     return value, rows
-
-
-class SliceLossFunction(torch.autograd.Function):
-    """mean_k W_p^p of the pooled rows [Xr; Xf] over the directions theta (None: the coordinate axes) as one autograd node,
-    shaped like PairLossFunction.
-
-    forward : pfm_slice_grad once: the value and, if an input requires a gradient, dL/dZ [N, d], which is kept
-    backward: dL/dZ times the incoming scalar, split into the real and the fake rows; theta is a constant"""
-
-    @staticmethod
-    def forward(ctx, p, theta, Xr, Xf):
-        nr = Xr.shape[0]
-        want = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
-        Z = torch.cat([Xr.detach(), Xf.detach()], dim=0).contiguous()
-        value, rows = _slice_call(p, Z, nr, theta, want)
-        ctx.nr = nr
-        if want:
-            ctx.save_for_backward(rows)
-        return value
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gL):
-        (rows,) = ctx.saved_tensors
-        G = rows * gL
-        return (None, None, G[:ctx.nr] if ctx.needs_input_grad[2] else None,
-                G[ctx.nr:] if ctx.needs_input_grad[3] else None)
 
 
 class ScoreFunction(torch.autograd.Function):
@@ -215,13 +173,25 @@ def _gammas(bandwidth):
     return out
 
 
-def _loss(kind, X_real, X_fake, bandwidth, standardize):
-    _m1d.check_bool(standardize, "standardize")
-    gammas = [] if kind == _lib.PERM_ENERGY or bandwidth is None else _gammas(bandwidth)
-    # the scaler runs as plain torch ops: autograd carries its derivative, and the upcast's
+def _pooled_inputs(X_real, X_fake, standardize):
+    """the two samples as float64 tensors on one HIP device, in their autograd graph: the scaler runs as plain torch ops, so
+    autograd carries its derivative, and the upcast's"""
     Xr, Xf = _boot.prepare(X_real, X_fake, NAMES, 1, standardize, graph=True)
     if Xr.shape[0] + Xf.shape[0] >= 2 ** 31:
         raise ValueError("at most 2**31 - 1 pooled samples, got %d" % (Xr.shape[0] + Xf.shape[0]))
+    return Xr, Xf
+
+
+def _order_p(p):
+    if not _m1d.is_int(p) or p not in (1, 2):
+        raise ValueError("p must be 1 or 2, got %r" % (p,))
+    return int(p)
+
+
+def _loss(kind, X_real, X_fake, bandwidth, standardize):
+    _m1d.check_bool(standardize, "standardize")
+    gammas = [] if kind == _lib.PERM_ENERGY or bandwidth is None else _gammas(bandwidth)
+    Xr, Xf = _pooled_inputs(X_real, X_fake, standardize)
     with torch.cuda.device(Xr.device):
         if kind == _lib.PERM_GAUSS and bandwidth is None:
             from . import twosample                    # (the permutation tests; imported where the median is asked for)
@@ -230,7 +200,7 @@ def _loss(kind, X_real, X_fake, bandwidth, standardize):
                 raise ValueError("the median pairwise distance is 0, so gamma = 1 / (2 median^2) is infinite (too few "
                                  "distinct rows)")
             gammas = _gammas(sigma)
-        return PairLossFunction.apply(kind, gammas, Xr, Xf)
+        return PooledLossFunction.apply(lambda Z, nr, want: _pair_call(kind, gammas, Z, nr, want), Xr, Xf)[0]
 
 
 def energy_loss(X_real, X_fake, standardize=False):
@@ -323,21 +293,19 @@ def sinkhorn_loss(X_real, X_fake, p=2, reg=0.1, epsilon=None, n_sinkhorn=100, st
     from . import sinkhorn as _sk                      # (the metric: its limits and eps = reg * median^p; imports twosample)
     _m1d.check_bool(standardize, "standardize")
     _m1d.check_bool(return_drift, "return_drift")
-    if not _m1d.is_int(p) or p not in (1, 2):
-        raise ValueError("p must be 1 or 2, got %r" % (p,))
+    p = _order_p(p)
     _m1d.check_positive(reg, "reg", reciprocal=True)
     _m1d.check_positive(epsilon, "epsilon", none_ok=True, reciprocal=True)
     if not _m1d.is_int(n_sinkhorn) or not 0 <= n_sinkhorn <= _sk.MAX_SINKHORN:
         raise ValueError("n_sinkhorn must be an integer in 0 .. %d, got %r" % (_sk.MAX_SINKHORN, n_sinkhorn))
-    Xr, Xf = _boot.prepare(X_real, X_fake, NAMES, 1, standardize, graph=True)
-    if Xr.shape[0] + Xf.shape[0] >= 2 ** 31:
-        raise ValueError("at most 2**31 - 1 pooled samples, got %d" % (Xr.shape[0] + Xf.shape[0]))
+    Xr, Xf = _pooled_inputs(X_real, X_fake, standardize)
     with torch.cuda.device(Xr.device):
         if epsilon is None:
             eps = float(_sk.epsilon_of(_sk._median(Xr.detach(), Xf.detach()), p, reg))     # one host read-back
         else:
             eps = float(epsilon)
-        value, drift = SinkhornLossFunction.apply(int(p), eps, int(n_sinkhorn), Xr, Xf)
+        n_sinkhorn = int(n_sinkhorn)
+        value, drift = PooledLossFunction.apply(lambda Z, nr, want: _sinkhorn_call(p, eps, n_sinkhorn, Z, nr, want), Xr, Xf)
     return (value, drift) if return_drift else value
 
 
@@ -355,12 +323,6 @@ def _features(X_real, X_fake):
     if sa[1] != sb[1]:
         raise ValueError("%s and %s have different numbers of features: %d and %d" % (NAMES[0], NAMES[1], sa[1], sb[1]))
     return sa[1]
-
-
-def _order_p(p):
-    if not _m1d.is_int(p) or p not in (1, 2):
-        raise ValueError("p must be 1 or 2, got %r" % (p,))
-    return int(p)
 
 
 def sliced_wasserstein_loss(X_real, X_fake, n_projections=64, p=2, directions=None, standardize=False):
@@ -398,9 +360,7 @@ def sliced_wasserstein_loss(X_real, X_fake, n_projections=64, p=2, directions=No
     d = _features(X_real, X_fake)
     if directions is not None:
         directions = _check_directions(directions, d)
-    Xr, Xf = _boot.prepare(X_real, X_fake, NAMES, 1, standardize, graph=True)
-    if Xr.shape[0] + Xf.shape[0] >= 2 ** 31:
-        raise ValueError("at most 2**31 - 1 pooled samples, got %d" % (Xr.shape[0] + Xf.shape[0]))
+    Xr, Xf = _pooled_inputs(X_real, X_fake, standardize)
     with torch.cuda.device(Xr.device):
         if directions is None:
             from . import wasserstein                  # (the metric: its draw of the directions)
@@ -408,7 +368,7 @@ def sliced_wasserstein_loss(X_real, X_fake, n_projections=64, p=2, directions=No
         if not isinstance(directions, torch.Tensor):
             directions = torch.from_numpy(np.array(directions, dtype=np.float64))        # (a copy: the caller's may be read-only)
         theta = directions.detach().to(device=Xr.device, dtype=torch.float64).contiguous()
-        return SliceLossFunction.apply(p, theta, Xr, Xf)
+        return PooledLossFunction.apply(lambda Z, nr, want: _slice_call(p, Z, nr, theta, want), Xr, Xf)[0]
 
 
 def wasserstein_1d_loss(X_real, X_fake, p=1):
@@ -431,11 +391,9 @@ def wasserstein_1d_loss(X_real, X_fake, p=1):
     d = _features(X_real, X_fake)
     if d > MAX_PROJECTIONS:
         raise ValueError("at most %d features, got %d" % (MAX_PROJECTIONS, d))
-    Xr, Xf = _boot.prepare(X_real, X_fake, NAMES, 1, False, graph=True)
-    if Xr.shape[0] + Xf.shape[0] >= 2 ** 31:
-        raise ValueError("at most 2**31 - 1 pooled samples, got %d" % (Xr.shape[0] + Xf.shape[0]))
+    Xr, Xf = _pooled_inputs(X_real, X_fake, False)
     with torch.cuda.device(Xr.device):
-        return SliceLossFunction.apply(p, None, Xr, Xf)
+        return PooledLossFunction.apply(lambda Z, nr, want: _slice_call(p, Z, nr, None, want), Xr, Xf)[0]
 
 
 def _check_nd(A, name, rank, what):

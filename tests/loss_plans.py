@@ -2,7 +2,7 @@
 branches the GPU tests of the losses must reach between them; no GPU, no package import.
 
   score_plan, score_variant    plan_of and launch_mode of probaforms_amd/metrics/csrc/pf_scoregrad.hip (pfm_score_grad)
-  slices, sweep_form           slices_of of pf_pairtile.h and the template choice of k_pair_sweep (pf_pairgrad.hip) and
+  slices, sweep_form           slices_of of pf_gradsweep.h and the template choice of k_pair_sweep (pf_pairgrad.hip) and
                                k_sinkhorn_sweep (pf_sinkgrad.hip)
   pair_grad_bytes, sinkhorn_grad_bytes    the workspace sizes those slices imply
 
