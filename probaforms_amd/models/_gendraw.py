@@ -8,15 +8,13 @@ What the reference's notebooks do by hand (docs/examples/regression.ipynb, forec
 -- as one call: the K noise draws are made on the CPU from torch's global generator exactly as K successive ``sample(C)``
 calls make them, stacked per window of draws and uploaded once per window; libpf_gendraw.so (gendraw_csrc/pf_gendraw.h)
 evaluates every draw and reduces across the draws on the device into the running-moment state of libpf_predict.so, whose
-pfp_finalize / pfp_quantiles finish the job.  Argument validation, the draw windows, the row chunks and the host loop are
-those of models/_predict.py.
+pfp_finalize / pfp_quantiles finish the job.  Argument validation, the draw windows, the row chunks, the driver
+(reduce_draws) and the host loop are those of models/_predict.py; this module gives it the generators' jobs as a source.
 """
 import torch
 
-from . import _predict
-from ._predict import (JointScores, JointSink, SampleScores, SampleStats, ScoreSink, _chunk_quantiles, draw_windows,
-                       joint_scores_of_draws, loop_draws, quantile_row_chunks, scores_of_draws, stats_of_draws, targets_on_host,
-                       validate, validate_joint, validate_scores)
+from ._predict import (JointScores, SampleScores, SampleStats, WindowedSource, as_numpy, joint_scores_of_draws, predictive,
+                       reduce_draws, scores_of_draws, stats_of_draws, targets_on_host, validate, validate_joint, validate_scores)
 
 
 def one_stream(n, width):
@@ -86,56 +84,23 @@ class AffineJob:
                                        k_lo, k_cnt, K, state, x_out, xt)
 
 
-def run(job, Cd, n, K, probs, ddof, want_stats, want_draws, scores=None, joint=None):
-    """-> (SampleStats of device tensors or None, draws [K, n, d] device tensor or None).  The caller has asked
-    job.supported().  Quantiles may force row chunks; every chunk then walks the same K noise draws (the generator is
-    rewound), so the draws are not kept in that case (want_draws and quantiles are separate public calls).
-    scores = (Y, fair): the scores path -- neither statistics nor draws; only the transposed draws are kept, per row chunk,
-    and the first item returned is a SampleScores of device tensors.  joint = (Y, fair, order): the same path with a
-    JointSink, and a JointScores of device tensors."""
-    from . import _predict_lib as pl
-    dev, d, width = job.device, job.d, job.width
-    f32 = dict(dtype=torch.float32, device=dev)
-    want_q = want_stats and probs is not None
-    x_out = torch.empty((K, n, d), **f32) if want_draws else None
-    state = pl.new_state(n, d, dev) if want_stats else None
-    q_out = torch.empty((len(probs), n, d), **f32) if want_q else None
-    probs_dev = torch.tensor(probs, dtype=torch.float64, device=dev) if want_q else None
-    sink = None
-    if scores is not None:
-        assert not (want_stats or want_draws)
-        sink = ScoreSink(scores[0], n, d, K, probs, scores[1], dev)
-    if joint is not None:
-        assert not (want_stats or want_draws) and scores is None
-        sink = JointSink(joint[0], n, d, K, joint[1], joint[2], dev)
-    want_xt = want_q or sink is not None
-    chunks = quantile_row_chunks(n, d, K, _predict.XT_CHUNK_BYTES) if want_xt else ([(0, n)] if n else [])
-    assert not (want_draws and len(chunks) > 1)
-    if n > 0:
-        windows = draw_windows(K, n, width, _predict.Z_WINDOW_BYTES)
-        job.prepare(Cd, n, max(cnt for _, cnt in windows))
-        start = torch.get_rng_state() if len(chunks) > 1 else None
-        for ci, (lo, m) in enumerate(chunks):
-            if ci > 0:
-                torch.set_rng_state(start)                        # every row chunk walks the same K draws
-            xt = torch.empty((m, d, K), **f32) if want_xt else None
-            for k_lo, k_cnt in windows:
-                zw = noise(k_cnt, n, width).to(dev)               # one upload per window
-                job.launch(lo, m, n, zw, k_lo, k_cnt, K, None if state is None else state[lo:lo + m],
-                           None if x_out is None else x_out[k_lo:k_lo + k_cnt], xt)
-            if sink is not None:
-                sink.chunk(pl, xt, lo, m)
-            elif xt is not None:
-                _chunk_quantiles(pl, xt, lo, m, d, K, probs_dev, q_out)
-    stats = None
-    if want_stats:
-        mean, std, mn, mx = (torch.empty((n, d), **f32) for _ in range(4))
+class JobSource(WindowedSource):
+    """a job as a source of _predict.reduce_draws(): a window's noise is made on the CPU as the model's sample makes it and
+    uploaded once"""
+
+    def __init__(self, job, Cd):
+        self.job, self.Cd, self.device, self.d, self.width = job, Cd, job.device, job.d, job.width
+
+    def open(self, n, K):
+        super().open(n, K)
         if n > 0:
-            pl.finalize(state, n, d, ddof, mean, std, mn, mx)
-        stats = SampleStats(mean, std, mn, mx, q_out)
-    if sink is not None:
-        return sink.result(), None
-    return stats, x_out
+            self.job.prepare(self.Cd, n, max(cnt for _, cnt in self.windows))
+
+    def noise(self, k_cnt):
+        return noise(k_cnt, self.n, self.width).to(self.device)
+
+    def launch(self, lo, m, zw, k_lo, k_cnt, state, x_out, xt):
+        self.job.launch(lo, m, self.n, zw, k_lo, k_cnt, self.K, state, x_out, xt)
 
 
 def _mismatch(C, c):
@@ -186,44 +151,37 @@ def job_of(model):
     raise TypeError("no generator draw kernel for %s" % type(model).__name__)
 
 
+def _predictive(model, C, K, host, kind, *args, **kwargs):
+    """predictive() of a generator: the job's kernels where they hold the shape (args: reduce_draws' after K), else the loop"""
+    job, conditions = job_of(model)
+
+    def kernel():
+        n, Cd = conditions(C)
+        return reduce_draws(JobSource(job, Cd), n, K, *args, **kwargs)[0 if kind is not None else 1]
+    return predictive(kernel if job.supported() else None, model.sample, C, K, host, kind, as_numpy)
+
+
 def sample_many(model, C, n_draws):
     """``np.array([model.sample(C) for _ in range(n_draws)])`` -> float32 numpy [n_draws, n, d]"""
     K, _ = validate(n_draws)
-    job, conditions = job_of(model)
-    if not job.supported():
-        return loop_draws(model.sample, C, K)
-    n, Cd = conditions(C)
-    return run(job, Cd, n, K, None, 0, False, True)[1].cpu().numpy()
+    return _predictive(model, C, K, lambda X: X, None, None, 0, False, True)
 
 
 def sample_stats(model, C, n_draws, quantiles, ddof):
     """SampleStats of float32 numpy arrays over n_draws samples per condition row"""
     K, probs = validate(n_draws, quantiles, ddof)
-    job, conditions = job_of(model)
-    if not job.supported():
-        return stats_of_draws(loop_draws(model.sample, C, K), probs, int(ddof))
-    n, Cd = conditions(C)
-    s = run(job, Cd, n, K, probs, int(ddof), True, False)[0]
-    return SampleStats(*(None if a is None else a.cpu().numpy() for a in s))
+    return _predictive(model, C, K, lambda X: stats_of_draws(X, probs, int(ddof)), SampleStats, probs, int(ddof), True, False)
 
 
 def sample_scores(model, C, Y, n_draws, quantiles, fair):
     """SampleScores of float32 numpy arrays: n_draws samples per condition row scored against the observed targets Y"""
     K, probs = validate_scores(n_draws, quantiles)
-    job, conditions = job_of(model)
-    if not job.supported():
-        return scores_of_draws(loop_draws(model.sample, C, K), targets_on_host(Y), probs, fair)
-    n, Cd = conditions(C)
-    s = run(job, Cd, n, K, probs, 0, False, False, scores=(Y, fair))[0]
-    return SampleScores(*(None if a is None else a.cpu().numpy() for a in s))
+    return _predictive(model, C, K, lambda X: scores_of_draws(X, targets_on_host(Y), probs, fair), SampleScores,
+                       probs, 0, False, False, scores=(Y, fair))
 
 
 def sample_joint_scores(model, C, Y, n_draws, fair, variogram_order):
     """JointScores of float32 numpy arrays [n]: n_draws samples per condition row scored as vectors against the targets Y"""
     K, order = validate_joint(n_draws, variogram_order)
-    job, conditions = job_of(model)
-    if not job.supported():
-        return joint_scores_of_draws(loop_draws(model.sample, C, K), targets_on_host(Y), fair, order)
-    n, Cd = conditions(C)
-    s = run(job, Cd, n, K, None, 0, False, False, joint=(Y, fair, order))[0]
-    return JointScores(*(None if a is None else a.cpu().numpy() for a in s))
+    return _predictive(model, C, K, lambda X: joint_scores_of_draws(X, targets_on_host(Y), fair, order), JointScores,
+                       None, 0, False, False, joint=(Y, fair, order))

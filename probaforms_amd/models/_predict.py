@@ -14,7 +14,10 @@ the same sort, one more pass over each sorted series.
 draws again, one workgroup per row over its K (K - 1) / 2 pairs.
 
 The arithmetic that needs no GPU lives here as plain functions (argument validation, the draw windows, the row chunks, the
-routing between the kernels and the host loop) so that the CPU suite covers it.
+routing between the kernels and the host loop) so that the CPU suite covers it.  So does the one driver of all four models'
+calls, reduce_draws(): it owns the outputs, the row chunks and torch's generator around them and takes the launches from a
+*source* (SeededFlow and HostPriorFlow here, _gendraw.JobSource) and the finishing kernels from `lib`, so that
+tests/test_predict_driver_host.py runs it on CPU tensors.  predictive() is the pattern of every public sample_* method.
 """
 import collections
 
@@ -236,14 +239,31 @@ def targets_on_device(Y, device):
     return Y.detach().to(device=device, dtype=torch.float32).contiguous()
 
 
+def _conditions(nf, C, eng):
+    if type(C) == type(1):            # python int only, as nflow.py:135
+        return C, None
+    return len(C), nf._on_device(C, eng)
+
+
+def _host_draws(n, d, dev):
+    """how the host prior makes one draw of randn(n, d): 'device' (the generator's bits drawn on the device) or 'host'"""
+    from .nflow import HostStreamOnDevice
+    return "device" if (n * d >= 16 and HostStreamOnDevice.usable(dev)) else "host"
+
+
+def targets_checked(Y, n, d, device):
+    """targets_on_device(Y); ValueError unless its shape is (n, d)"""
+    Y = targets_on_device(Y, device)
+    if tuple(Y.shape) != (n, d):
+        raise ValueError("Y must have shape (%d, %d) (one target per condition row and column), got %s" % (n, d, tuple(Y.shape)))
+    return Y
+
+
 class ScoreSink:
-    """the scores path of both run() functions: the device outputs, and pfp_scores on one row chunk's transposed draws"""
+    """the scores path of reduce_draws(): the device outputs, and pfp_scores on one row chunk's transposed draws"""
 
     def __init__(self, Y, n, d, K, probs, fair, device):
-        self.Y = targets_on_device(Y, device)
-        if tuple(self.Y.shape) != (n, d):
-            raise ValueError("Y must have shape (%d, %d) (one target per condition row and column), got %s"
-                             % (n, d, tuple(self.Y.shape)))
+        self.Y = targets_checked(Y, n, d, device)
         f32 = dict(dtype=torch.float32, device=device)
         self.n, self.d, self.K, self.fair = n, d, K, bool(fair)
         self.crps, self.pit = torch.empty((n, d), **f32), torch.empty((n, d), **f32)
@@ -269,14 +289,11 @@ class ScoreSink:
 
 
 class JointSink:
-    """the joint-scores path of both run() functions, with ScoreSink's protocol: the device outputs, and pfp_joint_scores on
-    one row chunk's transposed draws"""
+    """the joint-scores path of reduce_draws(), with ScoreSink's protocol: the device outputs, and pfp_joint_scores on one row
+    chunk's transposed draws"""
 
     def __init__(self, Y, n, d, K, fair, order, device):
-        self.Y = targets_on_device(Y, device)
-        if tuple(self.Y.shape) != (n, d):
-            raise ValueError("Y must have shape (%d, %d) (one target per condition row and column), got %s"
-                             % (n, d, tuple(self.Y.shape)))
+        self.Y = targets_checked(Y, n, d, device)
         f32 = dict(dtype=torch.float32, device=device)
         self.n, self.d, self.K, self.fair, self.order = n, d, K, bool(fair), order
         self.energy, self.spread = torch.empty((n,), **f32), torch.empty((n,), **f32)
@@ -291,34 +308,28 @@ class JointSink:
         return JointScores(self.energy, self.spread, self.variogram)
 
 
-def _conditions(nf, C, eng):
-    if type(C) == type(1):            # python int only, as nflow.py:135
-        return C, None
-    return len(C), nf._on_device(C, eng)
+def reduce_draws(source, n, K, probs, ddof, want_stats, want_draws, scores=None, joint=None, lib=None):
+    """K draws of each of n condition rows, reduced across the draws on the device -> (SampleStats of device tensors or None,
+    draws [K, n, d] device tensor or None).  scores = (Y, fair): the scores path -- neither statistics nor draws; only the
+    transposed draws are kept, per row chunk, and the first item returned is a SampleScores of device tensors.
+    joint = (Y, fair, order): the same path with a JointSink, and a JointScores of device tensors.
 
-
-def _host_draws(n, d, dev):
-    """how the host prior makes one draw of randn(n, d): 'device' (the generator's bits drawn on the device) or 'host'"""
-    from .nflow import HostStreamOnDevice
-    return "device" if (n * d >= 16 and HostStreamOnDevice.usable(dev)) else "host"
-
-
-def run(nf, C, K, probs, ddof, want_stats, want_draws, scores=None, joint=None):
-    """-> (SampleStats of device tensors or None, draws [K, n, d] device tensor or None).  The caller has checked route().
-    scores = (Y, fair): the scores path -- neither statistics nor draws; only the transposed draws are kept, per row chunk,
-    and the first item returned is a SampleScores of device tensors.  joint = (Y, fair, order): the same path with a
-    JointSink, and a JointScores of device tensors."""
-    from . import _predict_lib as pl
-    from .nflow import HostStreamOnDevice
-    eng = nf.engine()
-    eng.sync_params()
-    n, Cd = _conditions(nf, C, eng)
-    Cd = eng._cond(Cd, n)
-    dev, d = eng.device, eng.d
-    host = nf.prior.host_rng
+    `source` makes the draws; this function owns the outputs, the row chunks and torch's generator around them.  A source has
+    `device`, `d`, and
+        open(n, K)                      once, before any chunk and also when n == 0: only a source whose draws are K seeds
+                                        takes anything from torch's generator for n == 0
+        draw(lo, m, state, x_out, xt)   queues all K draws of rows lo .. lo + m: folded into state [m, d, ...] (or None), written
+                                        to x_out [K, n rows of this call, d] (or None) and transposed to xt [m, d, K] (or None)
+        close()                         once, after the last chunk's work is queued
+    Quantiles and scores may force row chunks; every chunk then walks the same K draws: the generator's state is saved before
+    the first chunk and put back before every later one, so the generator ends where K successive sample(C) calls leave it.  The
+    draws are not kept in that case.  `lib`: the _predict_lib module (None: import it); a CPU test hands in a stand-in."""
+    if lib is None:
+        from . import _predict_lib as lib
+    dev, d = source.device, source.d
     f32 = dict(dtype=torch.float32, device=dev)
     x_out = torch.empty((K, n, d), **f32) if want_draws else None
-    state = pl.new_state(n, d, dev) if want_stats else None
+    state = lib.new_state(n, d, dev) if want_stats else None
     q_out = torch.empty((len(probs), n, d), **f32) if (want_stats and probs is not None) else None
     probs_dev = torch.tensor(probs, dtype=torch.float64, device=dev) if q_out is not None else None
     sink = None
@@ -330,61 +341,27 @@ def run(nf, C, K, probs, ddof, want_stats, want_draws, scores=None, joint=None):
         sink = JointSink(joint[0], n, d, K, joint[1], joint[2], dev)
     want_xt = q_out is not None or sink is not None
     chunks = quantile_row_chunks(n, d, K, XT_CHUNK_BYTES) if want_xt else ([(0, n)] if n else [])
-    keep = []
-
-    def rows_of(t, lo, m):
-        return None if t is None else t[lo:lo + m]
-
-    if not host:
-        seeds = [nf.prior.next_seed() for _ in range(K)]          # what K successive sample() calls consume
-        for lo, m in chunks:
-            xt = torch.empty((m, d, K), **f32) if want_xt else None
-            keep.append(eng.predict_draw(rows_of(Cd, lo, m), m, lo, seeds, None, n, 0, K, K, rows_of(state, lo, m), x_out, xt))
-            if sink is not None:
-                sink.chunk(pl, xt, lo, m)
-            elif xt is not None:
-                _chunk_quantiles(pl, xt, lo, m, d, K, probs_dev, q_out)
-        torch.cuda.current_stream(dev).synchronize()             # the host seed arrays have been consumed
-    elif n > 0:
-        how = _host_draws(n, d, dev)
-        windows = draw_windows(K, n, d, Z_WINDOW_BYTES)
-        start = torch.get_rng_state() if len(chunks) > 1 else None
-        zbuf = torch.empty((windows[0][1], n, d), **f32)
-        for ci, (lo, m) in enumerate(chunks):
-            if ci > 0:
-                torch.set_rng_state(start)                        # every row chunk walks the same K draws of randn(n, d)
-            xt = torch.empty((m, d, K), **f32) if want_xt else None
-            hs = HostStreamOnDevice(dev).begin() if how == "device" else None
-            try:
-                for k_lo, k_cnt in windows:
-                    zw = zbuf[:k_cnt]
-                    if hs is not None:
-                        if (n * d) % 16 == 0:
-                            hs.draw(zw)                           # whole 16-blocks: k_cnt draws of n d numbers are one draw
-                        else:
-                            for k in range(k_cnt):
-                                hs.draw(zw[k])
-                    else:
-                        zw.copy_(torch.stack([torch.randn((n, d)) for _ in range(k_cnt)]))
-                    eng.predict_draw(rows_of(Cd, lo, m), m, lo, None, zw, n, k_lo, k_cnt, K, rows_of(state, lo, m),
-                                     None if x_out is None else x_out[k_lo:k_lo + k_cnt], xt)
-            finally:
-                if hs is not None:
-                    hs.end()
-            if sink is not None:
-                sink.chunk(pl, xt, lo, m)
-            elif xt is not None:
-                _chunk_quantiles(pl, xt, lo, m, d, K, probs_dev, q_out)
-    stats = None
-    if want_stats:
-        mean, std, mn, mx = (torch.empty((n, d), **f32) for _ in range(4))
-        if n > 0:
-            pl.finalize(state, n, d, ddof, mean, std, mn, mx)
-        stats = SampleStats(mean, std, mn, mx, q_out)
-    del keep
+    assert not (want_draws and len(chunks) > 1)
+    source.open(n, K)
+    start = torch.get_rng_state() if len(chunks) > 1 else None
+    for ci, (lo, m) in enumerate(chunks):
+        if ci > 0:
+            torch.set_rng_state(start)                            # every row chunk walks the same K draws
+        xt = torch.empty((m, d, K), **f32) if want_xt else None
+        source.draw(lo, m, None if state is None else state[lo:lo + m], x_out, xt)
+        if sink is not None:
+            sink.chunk(lib, xt, lo, m)
+        elif xt is not None:
+            _chunk_quantiles(lib, xt, lo, m, d, K, probs_dev, q_out)
+    source.close()
     if sink is not None:
         return sink.result(), None
-    return stats, x_out
+    if not want_stats:
+        return None, x_out
+    mean, std, mn, mx = (torch.empty((n, d), **f32) for _ in range(4))
+    if n > 0:
+        lib.finalize(state, n, d, ddof, mean, std, mn, mx)
+    return SampleStats(mean, std, mn, mx, q_out), x_out
 
 
 def _chunk_quantiles(pl, xt, lo, m, d, K, probs_dev, q_out):
@@ -397,6 +374,118 @@ def _chunk_quantiles(pl, xt, lo, m, d, K, probs_dev, q_out):
     q_out[:, lo:lo + m].copy_(t)
 
 
+class WindowedSource:
+    """A source of reduce_draws() whose draws come from noise made on torch's generator: the K draws of a chunk are made and
+    launched window by window (draw_windows: a window's noise [k_cnt, n, width] stays within Z_WINDOW_BYTES).  A subclass sets
+    device, d, width and gives noise(k_cnt) -> the next k_cnt draws of (n, width) normals on the device, and
+    launch(lo, m, zw, k_lo, k_cnt, state, x_out, xt) for draws k_lo .. k_lo + k_cnt of rows lo .. lo + m; begin() / end()
+    bracket a chunk's windows (end() also runs when a window raised).  Nothing touches the generator when n == 0."""
+
+    def open(self, n, K):
+        self.n, self.K = n, K
+        self.windows = draw_windows(K, n, self.width, Z_WINDOW_BYTES) if n > 0 else []
+
+    def begin(self):
+        pass
+    end = close = begin
+
+    def draw(self, lo, m, state, x_out, xt):
+        self.begin()
+        try:
+            for k_lo, k_cnt in self.windows:
+                self.launch(lo, m, self.noise(k_cnt), k_lo, k_cnt, state, None if x_out is None else x_out[k_lo:k_lo + k_cnt], xt)
+        finally:
+            self.end()
+
+
+class SeededFlow:
+    """the flow with the device prior: the K draws are K seeds of the counter-based stream (what K successive sample() calls
+    consume, taken even when n == 0) and one pfp_draw_accumulate per row chunk, which draws z inside the kernel"""
+
+    def __init__(self, nf, eng, Cd):
+        self.nf, self.eng, self.Cd, self.device, self.d = nf, eng, Cd, eng.device, eng.d
+
+    def open(self, n, K):
+        self.n, self.K = n, K
+        self.seeds = [self.nf.prior.next_seed() for _ in range(K)]
+        self.keep = []
+
+    def draw(self, lo, m, state, x_out, xt):
+        c = None if self.Cd is None else self.Cd[lo:lo + m]
+        self.keep.append(self.eng.predict_draw(c, m, lo, self.seeds, None, self.n, 0, self.K, self.K, state, x_out, xt))
+
+    def close(self):
+        torch.cuda.current_stream(self.device).synchronize()     # the host seed arrays have been consumed
+        del self.keep
+
+
+class HostPriorFlow(WindowedSource):
+    """the flow with the host prior: a window's z is k_cnt successive randn(n, d) of torch's generator, drawn on the device
+    with the generator's bits (HostStreamOnDevice, one state round trip per chunk) or on the host"""
+
+    def __init__(self, nf, eng, Cd):
+        self.eng, self.Cd, self.device, self.d, self.width = eng, Cd, eng.device, eng.d, eng.d
+
+    def open(self, n, K):
+        super().open(n, K)
+        if n > 0:
+            self.on_device = _host_draws(n, self.d, self.device) == "device"
+            self.zbuf = torch.empty((self.windows[0][1], n, self.d), dtype=torch.float32, device=self.device)
+
+    def begin(self):
+        from .nflow import HostStreamOnDevice
+        self.hs = HostStreamOnDevice(self.device).begin() if self.on_device else None
+
+    def end(self):
+        if self.hs is not None:
+            self.hs.end()
+
+    def noise(self, k_cnt):
+        zw = self.zbuf[:k_cnt]
+        if self.hs is None:
+            zw.copy_(torch.stack([torch.randn((self.n, self.d)) for _ in range(k_cnt)]))
+        elif (self.n * self.d) % 16 == 0:
+            self.hs.draw(zw)                                      # whole 16-blocks: k_cnt draws of n d numbers are one draw
+        else:
+            for k in range(k_cnt):
+                self.hs.draw(zw[k])
+        return zw
+
+    def launch(self, lo, m, zw, k_lo, k_cnt, state, x_out, xt):
+        c = None if self.Cd is None else self.Cd[lo:lo + m]
+        self.eng.predict_draw(c, m, lo, None, zw, self.n, k_lo, k_cnt, self.K, state, x_out, xt)
+
+
+def flow_draws(nf, C, K, *args, **kwargs):
+    """reduce_draws() of a flow whose route() is 'kernel': (C, K, probs, ddof, want_stats, want_draws, scores=, joint=)"""
+    eng = nf.engine()
+    eng.sync_params()
+    n, Cd = _conditions(nf, C, eng)
+    Cd = eng._cond(Cd, n)
+    source = (HostPriorFlow if nf.prior.host_rng else SeededFlow)(nf, eng, Cd)
+    return reduce_draws(source, n, K, *args, **kwargs)
+
+
 def loop_draws(sample, C, K):
     """the notebook's loop: K successive sample(C) calls, stacked [K, n, d] (numpy float32)"""
     return np.array([np.asarray(sample(C), dtype=np.float32) for _ in range(K)], dtype=np.float32)
+
+
+def as_numpy(a):
+    """a result array as numpy: a device tensor comes to the host, the host route's numpy passes"""
+    return a.cpu().numpy() if isinstance(a, torch.Tensor) else a
+
+
+def as_tensor_on(device):
+    """-> the conversion to a tensor on `device`: the host route's numpy goes there, a device tensor passes"""
+    return lambda a: a if isinstance(a, torch.Tensor) else torch.from_numpy(a).to(device)
+
+
+def predictive(kernel, sample, C, K, host, kind, convert):
+    """The pattern of every sample_* method.  kernel: () -> the device result (reduce_draws), or None when the call runs as
+    the notebook's loop on the host: K successive sample(C) calls, then host(X [K, n, d] numpy) -> the numpy result.  The
+    result is one array (kind None) or a named tuple `kind` whose fields may be None; convert is as_numpy or as_tensor_on()."""
+    s = kernel() if kernel is not None else host(loop_draws(sample, C, K))
+    if kind is None:
+        return convert(s)
+    return kind(*(None if a is None else convert(a) for a in s))

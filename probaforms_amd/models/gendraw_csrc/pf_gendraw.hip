@@ -21,27 +21,18 @@
 // (k_lo, k_cnt) alone.
 #include "../../csrc/rnvp_common.h"
 #include "pf_gendraw.h"
+#include "../predict_csrc/pf_drawfold.h"
 
 #include <math.h>
 
 namespace {
 
-using f4 = __attribute__((ext_vector_type(4))) float;
+using namespace drawfold;          // State, f4, mfma16, min_nan / max_nan, row_stride, load_state, emit_fold, store_state
 
 constexpr int kW = PFG_WAVES;
 constexpr int kThreads = 64 * kW;
-constexpr int kMaxGrid = 65536;
-constexpr int kLdsLimit = 160 * 1024;      // one CU's LDS on gfx950
 constexpr int kLdsWide = 80 * 1024;        // a pass of more than 16 draws only while two workgroups still fit a CU
 constexpr int kMaxLin = PFG_MAX_HIDDEN + 1;
-
-struct State {
-    double sum, sumsq;
-    float shift, mn, mx;
-    uint32_t count;
-};
-static_assert(sizeof(State) == PFP_STATE_BYTES, "state layout of pf_predict.h");
-constexpr int kStateFloats = (int)(sizeof(State) / sizeof(float));
 
 // the net as the kernels see it; offsets in floats
 struct Net {
@@ -96,9 +87,6 @@ int make_net(const pfg_mlp *m, Net *n) {
     return PFG_OK;
 }
 
-// row stride of an image [feature][RS] holding 16 NT draws: the four k rows a B read touches fall on distinct banks
-int row_stride(int nt) { return nt == 4 ? 80 : 16 * nt + 1; }
-
 // The LDS budget.  One wave's image: z [latent up to 4][RS], two ping-pong buffers [max(hmax, n_out) up to 4][RS] (a Linear
 // reads one and writes the other; the last one's output is what the fold reads), cb [hidden[0]], the row's state.
 int64_t image_floats(const Net &n, int RS, Geo *g) {
@@ -136,14 +124,8 @@ int pick_plan(const Net &n, int64_t k_cnt, Geo *g) {
     return 0;
 }
 
-__device__ __forceinline__ f4 mfma16(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
 // as pf_wgan.hip's act_exact: what the models' own sample computes
 __device__ __forceinline__ float act_exact(float v, int act) { return act == RNVP_ACT_TANH ? tanhf(v) : fmaxf(v, 0.f); }
-
-// numpy's min / max: NaN when either operand is NaN
-__device__ __forceinline__ float min_nan(float a, float b) { return (a != a || b != b) ? NAN : fminf(a, b); }
-__device__ __forceinline__ float max_nan(float a, float b) { return (a != a || b != b) ? NAN : fmaxf(a, b); }
 
 // the lanes of ONE wave agree on what they wrote to LDS (the LDS serves a wave's accesses in order)
 __device__ __forceinline__ void wave_sync() {
@@ -228,69 +210,6 @@ __device__ __forceinline__ void linear(const float *frag, int MT, int KS, int KG
     }
 }
 
-// One wave: the pass's draws X [d][RS] (ncols valid columns) to x_out / xt_out, and folded into the row's state ST (LDS).
-// Fold: lane (q, r) takes column 4 jj + q and draw 16 t + r; the 16 draws of a tile are reduced by a fixed xor butterfly
-// (float64 sums of x - shift and its square, float32 min / max), the tiles are added in draw order.
-template <int NT>
-__device__ __forceinline__ void emit_fold(const float *X, int RS, int d, int ncols, int64_t row, int64_t n_rows, int64_t k0,
-                                          int64_t k_lo, int64_t k_total, State *ST, bool fold, float *__restrict__ x_out,
-                                          float *__restrict__ xt_out, int lane) {
-    constexpr int NC = 16 * NT;
-    const int q = lane >> 4, r = lane & 15;
-    if (x_out) {
-        for (int e = lane; e < ncols * d; e += 64) {
-            const int col = e / d, j = e - col * d;
-            x_out[((k0 + col) * n_rows + row) * d + j] = X[j * RS + col];
-        }
-    }
-    if (xt_out) {
-        for (int e = lane; e < NC * d; e += 64) {
-            const int j = e / NC, col = e - j * NC;
-            if (col < ncols) xt_out[(row * d + j) * k_total + k_lo + k0 + col] = X[j * RS + col];
-        }
-    }
-    if (!fold) return;
-    for (int jj = 0; jj < d; jj += 4) {
-        const int j = jj + q;
-        const bool jok = j < d;
-        State st = ST[jok ? j : 0];
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            const int col = 16 * t + r;
-            const bool ok = jok && col < ncols;
-            const float v = X[(jok ? j : 0) * RS + col];
-            const float first = __shfl(v, lane & 48);           // the tile's first draw of this column
-            if (st.count == 0) st.shift = isfinite(first) ? first : 0.f;
-            const double dv = ok ? (double)v - (double)st.shift : 0.0;
-            double s1 = dv, s2 = dv * dv;
-            float mn = ok ? v : INFINITY, mx = ok ? v : -INFINITY;
-#pragma unroll
-            for (int w = 8; w >= 1; w >>= 1) {
-                s1 += __shfl_xor(s1, w);
-                s2 += __shfl_xor(s2, w);
-                mn = min_nan(mn, __shfl_xor(mn, w));
-                mx = max_nan(mx, __shfl_xor(mx, w));
-            }
-            const int nv = ncols - 16 * t;
-            if (nv > 0) {
-                st.sum += s1; st.sumsq += s2;
-                st.mn = min_nan(st.mn, mn); st.mx = max_nan(st.mx, mx);
-                st.count += (uint32_t)(nv < 16 ? nv : 16);
-            }
-        }
-        if (jok && r == 0) ST[j] = st;
-    }
-}
-
-__device__ __forceinline__ void load_state(State *ST, const State *state, int64_t row, int d, int lane) {
-    for (int j = lane; j < d; j += 64) {
-        State st = State{0.0, 0.0, 0.f, 0.f, 0.f, 0u};
-        if (state) st = state[row * d + j];
-        if (st.count == 0) { st.sum = 0.0; st.sumsq = 0.0; st.mn = INFINITY; st.mx = -INFINITY; }
-        ST[j] = st;
-    }
-}
-
 template <int NT, bool RESIDENT>
 __global__ void __launch_bounds__(kThreads)
 k_mlp_draw(Net n, Geo g, const float *__restrict__ params, const float *__restrict__ packed, const float *__restrict__ c,
@@ -341,8 +260,7 @@ k_mlp_draw(Net n, Geo g, const float *__restrict__ params, const float *__restri
             emit_fold<NT>(cur, RS, d, ncols, row, n_rows, k0, k_lo, k_total, ST, state != nullptr, x_out, xt_out, lane);
             wave_sync();
         }
-        if (state)
-            for (int j = lane; j < d; j += 64) state[row * d + j] = ST[j];
+        store_state(state, ST, row, d, lane);
         wave_sync();
     }
 }
@@ -402,8 +320,7 @@ k_affine_draw(int d, const float *__restrict__ mu, const float *__restrict__ sig
             emit_fold<1>(X, kARS, d, ncols, row, n_rows, k0, k_lo, k_total, ST, state != nullptr, x_out, xt_out, lane);
             wave_sync();
         }
-        if (state)
-            for (int j = lane; j < d; j += 64) state[row * d + j] = ST[j];
+        store_state(state, ST, row, d, lane);
         wave_sync();
     }
 }

@@ -341,6 +341,17 @@ class NormalizingFlow(nn.Module):
         from . import _predict
         return _predict.route(self, lambda: self.engine().predict_supported())
 
+    def _predictive(self, C, K, host, kind, *args, **kwargs):
+        """_predict.predictive() with device tensors: the kernels where route() allows (args: reduce_draws' after K), else the
+        loop of sample(C) on the host"""
+        from . import _predict
+        with torch.no_grad():
+            kernel = None
+            if self._predict_route() == "kernel":
+                kernel = lambda: _predict.flow_draws(self, C, K, *args, **kwargs)[0]
+            return _predict.predictive(kernel, lambda c: torch.as_tensor(self.sample(c)).detach().cpu().numpy(), C, K, host, kind,
+                                       _predict.as_tensor_on(DEVICE))
+
     def sample_many(self, C, n_draws):
         """``torch.stack([self.sample(C) for _ in range(n_draws)])`` -> [n_draws, n, var_size] on the device, in one
         launch per window of draws (pfp_draw_accumulate) instead of one per draw.  Consumes torch's global CPU generator
@@ -351,7 +362,7 @@ class NormalizingFlow(nn.Module):
         with torch.no_grad():
             if self._predict_route() != "kernel":
                 return torch.stack([torch.as_tensor(self.sample(C), dtype=torch.float32) for _ in range(K)])
-            return _predict.run(self, C, K, None, 0, False, True)[1]
+            return _predict.flow_draws(self, C, K, None, 0, False, True)[1]
 
     def sample_stats(self, C, n_draws=100, quantiles=None, ddof=0):
         """Per condition row, the statistics over ``n_draws`` samples that the reference's notebooks take from a Python loop
@@ -363,12 +374,8 @@ class NormalizingFlow(nn.Module):
         the kernel does not hold in LDS fall back to that loop on the host (``sample`` n_draws times plus numpy)."""
         from . import _predict
         K, probs = _predict.validate(n_draws, quantiles, ddof)
-        with torch.no_grad():
-            if self._predict_route() != "kernel":
-                X = _predict.loop_draws(lambda c: torch.as_tensor(self.sample(c)).detach().cpu().numpy(), C, K)
-                s = _predict.stats_of_draws(X, probs, ddof)
-                return _predict.SampleStats(*(None if a is None else torch.from_numpy(a).to(DEVICE) for a in s))
-            return _predict.run(self, C, K, probs, int(ddof), True, False)[0]
+        return self._predictive(C, K, lambda X: _predict.stats_of_draws(X, probs, int(ddof)), _predict.SampleStats,
+                                probs, int(ddof), True, False)
 
     def sample_scores(self, C, Y, n_draws=1000, quantiles=(0.05, 0.95), fair=False):
         """Per condition row and column, the scores of ``n_draws`` samples against the observed targets ``Y`` [n, var_size]:
@@ -382,12 +389,8 @@ class NormalizingFlow(nn.Module):
         fall back to that loop on the host (``sample`` n_draws times plus numpy)."""
         from . import _predict
         K, probs = _predict.validate_scores(n_draws, quantiles)
-        with torch.no_grad():
-            if self._predict_route() != "kernel":
-                X = _predict.loop_draws(lambda c: torch.as_tensor(self.sample(c)).detach().cpu().numpy(), C, K)
-                s = _predict.scores_of_draws(X, _predict.targets_on_host(Y), probs, fair)
-                return _predict.SampleScores(*(None if a is None else torch.from_numpy(a).to(DEVICE) for a in s))
-            return _predict.run(self, C, K, probs, 0, False, False, scores=(Y, fair))[0]
+        return self._predictive(C, K, lambda X: _predict.scores_of_draws(X, _predict.targets_on_host(Y), probs, fair),
+                                _predict.SampleScores, probs, 0, False, False, scores=(Y, fair))
 
     def sample_joint_scores(self, C, Y, n_draws=1000, fair=False, variogram_order=0.5):
         """Per condition row, the joint scores of ``n_draws`` samples, taken as vectors in R^var_size, against the observed
@@ -401,12 +404,8 @@ class NormalizingFlow(nn.Module):
         fall back to that loop on the host (``sample`` n_draws times plus numpy)."""
         from . import _predict
         K, order = _predict.validate_joint(n_draws, variogram_order)
-        with torch.no_grad():
-            if self._predict_route() != "kernel":
-                X = _predict.loop_draws(lambda c: torch.as_tensor(self.sample(c)).detach().cpu().numpy(), C, K)
-                s = _predict.joint_scores_of_draws(X, _predict.targets_on_host(Y), fair, order)
-                return _predict.JointScores(*(None if a is None else torch.from_numpy(a).to(DEVICE) for a in s))
-            return _predict.run(self, C, K, None, 0, False, False, joint=(Y, fair, order))[0]
+        return self._predictive(C, K, lambda X: _predict.joint_scores_of_draws(X, _predict.targets_on_host(Y), fair, order),
+                                _predict.JointScores, None, 0, False, False, joint=(Y, fair, order))
 
     # -- host staging (SURVEY.md 8(f) rank 3) -------------------------------------------------
     # one chunk of output rows: at least PIPELINE_CHUNK_BYTES and at least PIPELINE_MIN_ROWS rows (a launch of fewer

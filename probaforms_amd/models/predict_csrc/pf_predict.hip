@@ -28,28 +28,16 @@
 #include "../../csrc/rnvp_common.h"
 #include "../../csrc/rnvp_generic_net.h"
 #include "../../csrc/rnvp_prior.h"
-#include "pf_predict.h"
+#include "pf_drawfold.h"
 
 #include <math.h>
 
 namespace {
 
 using rnvp::KShape;
-using f4 = __attribute__((ext_vector_type(4))) float;
+using namespace drawfold;          // State, f4, mfma16, min_nan / max_nan, row_stride, load_state, emit_fold, store_state
 
-constexpr int kMaxGrid = 65536;
-constexpr int kLdsLimit = 160 * 1024;      // one CU's LDS on gfx950
 constexpr int kLdsWide = 40 * 1024;        // a pass of more than 16 draws only while four waves still fit a CU
-
-struct State {
-    double sum, sumsq;
-    float shift, mn, mx;
-    uint32_t count;
-};
-static_assert(sizeof(State) == PFP_STATE_BYTES, "state layout");
-
-// row stride of an image [feature][RS] holding 16 NT draws: the four k rows a B read touches fall on distinct banks
-template <int NT> struct Rs { static constexpr int v = NT == 4 ? 80 : 16 * NT + 1; };
 
 // float offsets of one wave's LDS images
 struct Geo {
@@ -68,16 +56,10 @@ Geo make_geo(const KShape &s, int RS) {
     g.oH1 = o; o += (s.nh > 1 ? hp : 0) * RS;
     g.oCB = o; o += s.L * 2 * s.nout[0];
     o = (o + 3) / 4 * 4;
-    g.oST = o; o += s.d * (int)(sizeof(State) / sizeof(float));
+    g.oST = o; o += s.d * kStateFloats;
     g.floats = o;
     return g;
 }
-
-__device__ __forceinline__ f4 mfma16(float a, float b, f4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-// numpy's min / max: NaN when either operand is NaN (fminf / fmaxf return the other operand)
-__device__ __forceinline__ float min_nan(float a, float b) { return (a != a || b != b) ? NAN : fminf(a, b); }
-__device__ __forceinline__ float max_nan(float a, float b) { return (a != a || b != b) ? NAN : fmaxf(a, b); }
 
 __device__ __forceinline__ float mask_of(const KShape &s, const uint8_t *__restrict__ masks, int l, int j) {
     if (masks) return (float)masks[l * s.d + j];
@@ -89,7 +71,7 @@ __device__ __forceinline__ float mask_of(const KShape &s, const uint8_t *__restr
 template <int NT>
 __device__ __forceinline__ void linear(const float *__restrict__ W, int ldw, int nin, int nout, const float *bias,
                                        const float *in, float *out, int act, int lane) {
-    constexpr int RS = Rs<NT>::v;
+    constexpr int RS = row_stride(NT);
     const int q = lane >> 4, r = lane & 15;
     const int MT = (nout + 15) >> 4, KS = (nin + 3) >> 2;
     for (int m = 0; m < MT; ++m) {
@@ -149,8 +131,8 @@ k_draw(KShape s, Geo g, const float *__restrict__ params, const uint8_t *__restr
        int64_t n_rows, int64_t row_offset, const uint64_t *__restrict__ seeds, const float *__restrict__ z, int64_t n_total,
        int64_t k_lo, int64_t k_cnt, int64_t k_total, State *state, float *x_out, float *xt_out) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    constexpr int RS = Rs<NT>::v, NC = 16 * NT;
-    const int lane = threadIdx.x, q = lane >> 4, r = lane & 15, d = s.d, cd = s.c, h0 = s.nout[0];
+    constexpr int RS = row_stride(NT), NC = 16 * NT;
+    const int lane = threadIdx.x, d = s.d, cd = s.c, h0 = s.nout[0];
     float *X = lds + g.oX, *XM = lds + g.oXM, *T = lds + g.oT, *S = lds + g.oS, *H0 = lds + g.oH0, *H1 = lds + g.oH1;
     float *CB = lds + g.oCB;
     State *ST = reinterpret_cast<State *>(lds + g.oST);
@@ -167,12 +149,7 @@ k_draw(KShape s, Geo g, const float *__restrict__ params, const uint8_t *__restr
             for (int i = 0; i < cd; ++i) a = fmaf(w[i], c[row * cd + i], a);
             CB[e] = a;
         }
-        for (int j = lane; j < d; j += 64) {
-            State st = State{0.0, 0.0, 0.f, 0.f, 0.f, 0u};
-            if (state) st = state[row * d + j];
-            if (st.count == 0) { st.sum = 0.0; st.sumsq = 0.0; st.mn = INFINITY; st.mx = -INFINITY; }
-            ST[j] = st;
-        }
+        load_state(ST, state, row, d, lane);
         __syncthreads();
         for (int64_t k0 = 0; k0 < k_cnt; k0 += NC) {
             const int ncols = (int)(k_cnt - k0 < NC ? k_cnt - k0 : NC);
@@ -223,55 +200,10 @@ k_draw(KShape s, Geo g, const float *__restrict__ params, const uint8_t *__restr
                 }
                 __syncthreads();
             }
-            if (x_out) {
-                for (int e = lane; e < ncols * d; e += 64) {
-                    const int col = e / d, j = e - col * d;
-                    x_out[((k0 + col) * n_rows + row) * d + j] = X[j * RS + col];
-                }
-            }
-            if (xt_out) {
-                for (int e = lane; e < NC * d; e += 64) {
-                    const int j = e / NC, col = e - j * NC;
-                    if (col < ncols) xt_out[(row * d + j) * k_total + k_lo + k0 + col] = X[j * RS + col];
-                }
-            }
-            if (state) {
-                // lane (q, r): column 4 jj + q, draw 16 t + r; a fixed xor butterfly over the 16 draws, tiles folded in order
-                for (int jj = 0; jj < d; jj += 4) {
-                    const int j = jj + q;
-                    const bool jok = j < d;
-                    State st = ST[jok ? j : 0];
-#pragma unroll
-                    for (int t = 0; t < NT; ++t) {
-                        const int col = 16 * t + r;
-                        const bool ok = jok && col < ncols;
-                        const float v = X[(jok ? j : 0) * RS + col];
-                        const float first = __shfl(v, lane & 48);
-                        if (st.count == 0) st.shift = isfinite(first) ? first : 0.f;
-                        const double dv = ok ? (double)v - (double)st.shift : 0.0;
-                        double s1 = dv, s2 = dv * dv;
-                        float mn = ok ? v : INFINITY, mx = ok ? v : -INFINITY;
-#pragma unroll
-                        for (int w = 8; w >= 1; w >>= 1) {
-                            s1 += __shfl_xor(s1, w);
-                            s2 += __shfl_xor(s2, w);
-                            mn = min_nan(mn, __shfl_xor(mn, w));
-                            mx = max_nan(mx, __shfl_xor(mx, w));
-                        }
-                        const int nv = ncols - 16 * t;
-                        if (nv > 0) {
-                            st.sum += s1; st.sumsq += s2;
-                            st.mn = min_nan(st.mn, mn); st.mx = max_nan(st.mx, mx);
-                            st.count += (uint32_t)(nv < 16 ? nv : 16);
-                        }
-                    }
-                    if (jok && r == 0) ST[j] = st;
-                }
-            }
+            emit_fold<NT>(X, RS, d, ncols, row, n_rows, k0, k_lo, k_total, ST, state != nullptr, x_out, xt_out, lane);
             __syncthreads();
         }
-        if (state)
-            for (int j = lane; j < d; j += 64) state[row * d + j] = ST[j];
+        store_state(state, ST, row, d, lane);
         __syncthreads();
     }
 }
@@ -436,8 +368,7 @@ k_scores(const float *__restrict__ xt, const float *__restrict__ y, int64_t n_se
 int pick_tiles(const KShape &s, int64_t k_cnt, size_t *bytes) {
     const int want = k_cnt > 32 ? 4 : (k_cnt > 16 ? 2 : 1);
     for (int nt = want; nt >= 1; nt >>= 1) {
-        const int RS = nt == 4 ? Rs<4>::v : (nt == 2 ? Rs<2>::v : Rs<1>::v);
-        const size_t b = (size_t)make_geo(s, RS).floats * sizeof(float);
+        const size_t b = (size_t)make_geo(s, row_stride(nt)).floats * sizeof(float);
         if (b <= (size_t)(nt > 1 ? kLdsWide : kLdsLimit)) { *bytes = b; return nt; }
     }
     return 0;
@@ -457,7 +388,7 @@ int launch_draw(hipStream_t st, const KShape &k, size_t lds, int grid, const flo
                 int64_t n_rows, int64_t row_offset, const uint64_t *seeds, const float *z, int64_t n_total, int64_t k_lo,
                 int64_t k_cnt, int64_t k_total, State *state, float *x_out, float *xt_out) {
     constexpr int slot = NT == 4 ? 2 : NT - 1;
-    const Geo g = make_geo(k, Rs<NT>::v);
+    const Geo g = make_geo(k, row_stride(NT));
     if (lds > 48 * 1024) {
         const int e = rnvp::allow_big_lds(reinterpret_cast<const void *>(&k_draw<NT>), (int)lds, g_big[slot]);
         if (e != RNVP_OK) return e;

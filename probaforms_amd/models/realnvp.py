@@ -277,6 +277,15 @@ class RealNVP(GenModel):
             X = self.nf.sample(C).cpu().detach().numpy()
         return X
 
+    def _predictive(self, C, K, kernel, host, kind=None):
+        """_predict.predictive() with numpy results: kernel(C on the device) -> self.nf's device result where its route allows,
+        else host(the stacked draws of the loop of self.sample)"""
+        from . import _predict
+        on_device = None
+        if self.nf._predict_route() == "kernel":
+            on_device = lambda: kernel(C if type(C) == type(1) else _to_device_f32(C, self.nf.engine().device))
+        return _predict.predictive(on_device, self.sample, C, K, host, kind, _predict.as_numpy)
+
     def sample_many(self, C=100, n_draws=100):
         """``np.array([self.sample(C) for _ in range(n_draws)])`` -> float32 numpy [n_draws, n, d] (a name the reference does not have):
         the draws of the notebooks' predictive loop in one launch per window of draws.  Consumes torch's global CPU
@@ -284,11 +293,7 @@ class RealNVP(GenModel):
         in LDS run the loop itself."""
         from . import _predict
         K, _ = _predict.validate(n_draws)
-        if self.nf._predict_route() != "kernel":
-            return _predict.loop_draws(self.sample, C, K)
-        if type(C) != type(1):
-            C = _to_device_f32(C, self.nf.engine().device)
-        return self.nf.sample_many(C, K).cpu().numpy()
+        return self._predictive(C, K, lambda c: self.nf.sample_many(c, K), lambda X: X)
 
     def sample_stats(self, C=100, n_draws=100, quantiles=None, ddof=0):
         """Predictive statistics per condition row over ``n_draws`` samples (a name the reference does not have): what
@@ -303,12 +308,8 @@ class RealNVP(GenModel):
         in LDS fall back to the loop on the host (``self.sample`` n_draws times plus numpy), so the call always works."""
         from . import _predict
         K, probs = _predict.validate(n_draws, quantiles, ddof)
-        if self.nf._predict_route() != "kernel":
-            return _predict.stats_of_draws(_predict.loop_draws(self.sample, C, K), probs, int(ddof))
-        if type(C) != type(1):
-            C = _to_device_f32(C, self.nf.engine().device)
-        s = self.nf.sample_stats(C, K, probs, int(ddof))
-        return _predict.SampleStats(*(None if a is None else a.cpu().numpy() for a in s))
+        return self._predictive(C, K, lambda c: self.nf.sample_stats(c, K, probs, int(ddof)),
+                                lambda X: _predict.stats_of_draws(X, probs, int(ddof)), _predict.SampleStats)
 
     def sample_scores(self, C, Y, n_draws=1000, quantiles=(0.05, 0.95), fair=False):
         """Scores of the predictive distribution of every condition row against what was observed (a name the reference does
@@ -328,12 +329,8 @@ class RealNVP(GenModel):
         (``self.sample`` n_draws times plus numpy), so the call always works."""
         from . import _predict
         K, probs = _predict.validate_scores(n_draws, quantiles)
-        if self.nf._predict_route() != "kernel":
-            return _predict.scores_of_draws(_predict.loop_draws(self.sample, C, K), _predict.targets_on_host(Y), probs, fair)
-        if type(C) != type(1):
-            C = _to_device_f32(C, self.nf.engine().device)
-        s = self.nf.sample_scores(C, Y, K, probs, fair)
-        return _predict.SampleScores(*(None if a is None else a.cpu().numpy() for a in s))
+        return self._predictive(C, K, lambda c: self.nf.sample_scores(c, Y, K, probs, fair),
+                                lambda X: _predict.scores_of_draws(X, _predict.targets_on_host(Y), probs, fair), _predict.SampleScores)
 
     def sample_joint_scores(self, C, Y, n_draws=1000, fair=False, variogram_order=0.5):
         """Scores of the JOINT predictive distribution of every condition row against what was observed (a name the reference
@@ -353,12 +350,9 @@ class RealNVP(GenModel):
         (``self.sample`` n_draws times plus numpy), so the call always works."""
         from . import _predict
         K, order = _predict.validate_joint(n_draws, variogram_order)
-        if self.nf._predict_route() != "kernel":
-            return _predict.joint_scores_of_draws(_predict.loop_draws(self.sample, C, K), _predict.targets_on_host(Y), fair, order)
-        if type(C) != type(1):
-            C = _to_device_f32(C, self.nf.engine().device)
-        s = self.nf.sample_joint_scores(C, Y, K, fair, order)
-        return _predict.JointScores(*(None if a is None else a.cpu().numpy() for a in s))
+        return self._predictive(C, K, lambda c: self.nf.sample_joint_scores(c, Y, K, fair, order),
+                                lambda X: _predict.joint_scores_of_draws(X, _predict.targets_on_host(Y), fair, order),
+                                _predict.JointScores)
 
     def _sample_sharded(self, C, n, rank, world, gather):
         import torch.distributed as dist

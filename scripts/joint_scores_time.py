@@ -43,7 +43,7 @@ def device_draws(m, C, K):
         return m.nf.sample_many(torch.from_numpy(C).cuda(), K)
     job, conditions = _gendraw.job_of(m)
     n, Cd = conditions(C)
-    return _gendraw.run(job, Cd, n, K, None, 0, False, True)[1]
+    return _gendraw.reduce_draws(_gendraw.JobSource(job, Cd), n, K, None, 0, False, True)[1]
 
 
 def torch_scores(X, Y):
