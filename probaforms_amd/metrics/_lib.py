@@ -27,6 +27,7 @@ PAIR_MAX_GAMMAS = 8        # PFM_PAIR_MAX_GAMMAS: Gaussians in pfm_pair_grad's k
 SLICE_LDS_ROWS = 13312     # PFM_SLICE_LDS_ROWS: rows per sample pfm_slice_grad sorts itself, in LDS
 SCORE_MAX_K = 1024         # PFM_SCORE_MAX_K: draws per row of pfm_score_grad
 SCORE_MAX_KD = 16384       # PFM_SCORE_MAX_KD: draws times features of pfm_score_grad (a row's draws in LDS)
+VARIO_MAX_D = 64           # PFM_VARIO_MAX_D: features of pfm_variogram_grad (a row's pair table in LDS beside its draws)
 PFM_EINVAL, PFM_EUNSUPPORTED, PFM_EWORKSPACE = -1, -2, -3
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -71,6 +72,9 @@ _SIGNATURES = {
     "pfm_score_grad_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
     "pfm_score_plan": (C.c_int, [_I64, _I64, _I64, _VP]),
     "pfm_score_grad": (C.c_int, [_VP, _VP, _VP, _I64, _I64, _I64, C.c_int, _VP, _VP, _VP, _VP, _VP, _SZ]),
+    "pfm_variogram_grad_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
+    "pfm_variogram_plan": (C.c_int, [_I64, _I64, _I64, _VP]),
+    "pfm_variogram_grad": (C.c_int, [_VP, _VP, _VP, _VP, _I64, _I64, _I64, C.c_double, _VP, _VP, _VP, _VP, _SZ]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -424,3 +428,40 @@ def score_grad_status(X, Y, fair, scores, spread, grad_x, grad_y, ws):
 
 def score_grad(*args):
     check(score_grad_status(*args), "pfm_score_grad")
+
+
+def variogram_grad_workspace_bytes(n, K, d):
+    return int(lib().pfm_variogram_grad_workspace_bytes(int(n), int(K), int(d)))
+
+
+def variogram_plan_status(n, K, d):
+    """-> (status, (rows per workgroup, lanes that share a row, LDS bytes, workgroups, rows in flight, slices of the draws)): how
+    pfm_variogram_grad tiles a call; no device is touched"""
+    plan = (C.c_int64 * 6)()
+    st = int(lib().pfm_variogram_plan(int(n), int(K), int(d), C.cast(plan, _VP)))
+    return st, tuple(int(v) for v in plan)
+
+
+def variogram_plan(n, K, d):
+    st, plan = variogram_plan_status(n, K, d)
+    check(st, "pfm_variogram_plan")
+    return plan
+
+
+def variogram_grad_status(X, Y, W, order, scores, grad_x, grad_y, ws):
+    """enqueue the per-row variogram scores [n] of order 0.5, 1 or 2 of the draws X [K, n, d] against the targets Y [n, d] under the
+    weights W [d, d] (None: all 1) and, where given, the derivatives grad_x [K, n, d], grad_y [n, d] on the current stream and
+    return the status"""
+    K, n, d = X.shape
+    assert tuple(Y.shape) == (n, d) and scores.numel() == n and (W is None or tuple(W.shape) == (d, d))
+    assert (grad_x is None or tuple(grad_x.shape) == (K, n, d)) and (grad_y is None or tuple(grad_y.shape) == (n, d))
+    return int(lib().pfm_variogram_grad(torch.cuda.current_stream().cuda_stream, _ptr(X, torch.float64, "X_draws"),
+                                        _ptr(Y, torch.float64, "Y"), _ptr(W, torch.float64, "weights", nullable=True), n, K, d,
+                                        float(order), _ptr(scores, torch.float64, "scores"),
+                                        _ptr(grad_x, torch.float64, "grad_x", nullable=True),
+                                        _ptr(grad_y, torch.float64, "grad_y", nullable=True), _ptr(ws, torch.uint8, "workspace"),
+                                        ws.numel()))
+
+
+def variogram_grad(*args):
+    check(variogram_grad_status(*args), "pfm_variogram_grad")

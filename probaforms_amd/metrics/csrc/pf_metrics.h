@@ -42,6 +42,9 @@
  *   pfm_score_grad    per row, the energy score of the row's K draws against the row's target TOGETHER WITH its derivative by
  *                     every draw and by the target: the loss a conditional sampler is trained on, one sweep over each row's
  *                     K (K - 1) / 2 pairs in LDS; pfm_score_plan says how a shape is tiled
+ *   pfm_variogram_grad per row, the variogram score of the row's K draws against the row's target TOGETHER WITH its derivative by
+ *                     every draw and by the target: the score that reacts to the dependence between the features; a row's
+ *                     d (d - 1) / 2 pair terms stay in LDS; pfm_variogram_plan says how a shape is tiled
  *
  * Conventions (as include/rnvp_hip.h)
  *   - every pointer is a DEVICE pointer (but pfm_pair_grad's `gammas`); sizes are plain integers;
@@ -433,6 +436,51 @@ int pfm_score_plan(int64_t n, int64_t K, int64_t d, int64_t *plan);
  */
 int pfm_score_grad(void *stream, const double *X, const double *Y, int64_t n, int64_t K, int64_t d, int fair, double *scores,
                    double *spread, double *grad_x, double *grad_y, void *workspace, size_t workspace_bytes);
+
+/* ---- differentiable per-row scoring rule: the variogram score of K draws (pf_variogram.hip) -------- */
+
+#define PFM_VARIO_MAX_D 64          /* features of pfm_variogram_grad: a row's d (d - 1) / 2 pair terms stay in LDS beside its draws */
+
+/* bytes of workspace pfm_variogram_grad needs: nothing is kept there, the figure is the least a caller can allocate (0: the
+   arguments are invalid or outside the limits) */
+size_t pfm_variogram_grad_workspace_bytes(int64_t n, int64_t K, int64_t d);
+
+/*
+ * How pfm_variogram_grad tiles a call of n rows, K draws and d features; needs no device.  plan is a HOST array of 6:
+ *   plan[0]  R: the consecutive rows of a workgroup (for every draw, one contiguous run of R d doubles of X and of grad_x)
+ *   plan[1]  S: the lanes that share one row, a power of two, min(256, the least >= K); a lane owns ceil(K / S) draws
+ *   plan[2]  the dynamic LDS bytes of a workgroup, at most 163840
+ *   plan[3]  the workgroups, ceil(n / R)
+ *   plan[4]  G: the rows in flight at a time, 256 / S or fewer where LDS holds fewer (every one keeps its pair table there)
+ *   plan[5]  T: the slices the draws are cut into while a row's pair sums are formed, S / (d (d - 1) / 2) where that is above 1
+ * d = 1 has no pair: a lane per row, R = G = 256, S = T = 1, no LDS.
+ * R depends on n (fewer rows per workgroup while the workgroups are few); no output of pfm_variogram_grad does.
+ * The statuses are pfm_variogram_grad's for the sizes; PFM_EINVAL for a NULL plan.
+ */
+int pfm_variogram_plan(int64_t n, int64_t K, int64_t d, int64_t *plan);
+
+/*
+ * The variogram score (Scheuerer & Hamill 2015) of every row's K draws against the row's target, and its derivatives.  X [K, n, d]
+ * holds draw k of row r at X[k, r, :], Y [n, d] the targets, W [d, d] the weights (NULL: all 1; used as given, symmetric or not,
+ * of either sign).  Per row, with x_k = X[k, r, :], y = Y[r, :] and order p = 0.5, 1 or 2:
+ *   v_ij = |y_i - y_j|^p,   m_ij = (1 / K) sum_k |x_ki - x_kj|^p,   r_ij = v_ij - m_ij
+ *   scores[r]       = sum_i sum_j W_ij r_ij^2                                            (formed as sum_{i < j} (W_ij + W_ji) r_ij r_ij)
+ *   grad_x[k, r, i] = -(2 / K) sum_j (W_ij + W_ji) r_ij h(x_ki - x_kj)                   = d scores[r] / d X[k, r, i]
+ *   grad_y[r, i]    =  2       sum_j (W_ij + W_ji) r_ij h(y_i - y_j)                     = d scores[r] / d Y[r, i]
+ *   h(t) = 2 t (p = 2);  sgn t (p = 1);  sgn t / (2 sqrt|t|) (p = 0.5);  for p = 1 and 0.5 exactly 0 at t = 0 (the subgradient: no
+ *   0 times infinity is formed).  For p = 0.5 h grows without bound as two coordinates of a draw approach each other.
+ * |.|^p is a square root, the identity or a square, never pow, and every difference is taken on the values themselves.
+ * grad_x [K, n, d] and grad_y [n, d] may each be NULL; with both NULL only the values are formed.
+ * Nothing is checked for NaN or infinity: a NaN in a row's draws or target makes that row's score and all its gradients NaN and
+ * reaches no other row.  No float atomics, and nothing is kept in the workspace; the order of every sum depends on (K, d) only, so a
+ * row's outputs are bitwise the same at any position of the row, for any n, in any call, whichever outputs are asked for.  On
+ * success every element of every output given is written.
+ * PFM_EINVAL for n, K or d < 1, n >= 2^31, an order other than 0.5, 1 or 2, a NULL X, Y or scores; PFM_EUNSUPPORTED for
+ * d > PFM_VARIO_MAX_D, K > PFM_SCORE_MAX_K or K d > PFM_SCORE_MAX_KD; PFM_EWORKSPACE for a missing or short workspace; on any error
+ * nothing is written.
+ */
+int pfm_variogram_grad(void *stream, const double *X, const double *Y, const double *W, int64_t n, int64_t K, int64_t d,
+                       double order, double *scores, double *grad_x, double *grad_y, void *workspace, size_t workspace_bytes);
 
 /* ---- nearest-neighbour two-sample test (pf_nn.hip) ------------------------------------------------ */
 

@@ -39,6 +39,13 @@ energy score (Gneiting & Raftery 2007) of the row's K draws against the row's ob
 sample_joint_scores and sample_scores report as metrics, with a backward().  The four above compare two pooled samples; these give
 every row its own signal and cost K^2 pairs per row, not n^2.  Value and gradients come from one sweep over each row's pairs in LDS;
 nothing of size K^2 is stored, for the forward or for the backward.
+
+variogram_score_loss is the third conditional member (kernel: csrc/pf_variogram.hip, pfm_variogram_grad): per condition row the
+variogram score (Scheuerer & Hamill 2015) of the row's K draws against the row's target, the `variogram` of sample_joint_scores
+with a backward().  The energy score hardly separates predictive laws that differ only in the dependence between the features and
+the CRPS is blind to it; the variogram score reacts to it, and is trained as energy_score_loss + lambda * variogram_score_loss.  A
+row's d (d - 1) / 2 pair terms stay in LDS beside its draws: nothing of size K d^2 or n d^2 is stored, for the forward or for the
+backward.
 """
 import math
 
@@ -151,6 +158,34 @@ class ScoreFunction(torch.autograd.Function):
         gx, gy = ctx.saved_tensors
         return (None, gx * gS[None, :, None] if ctx.needs_input_grad[1] else None,
                 gy * gS[:, None] if ctx.needs_input_grad[2] else None)
+
+
+class VariogramFunction(torch.autograd.Function):
+    """The per-row variogram scores [n] of the draws X [K, n, d] against the targets Y [n, d] as one autograd node.
+
+    forward : pfm_variogram_grad once: the scores and, for whichever of X and Y requires a gradient, the unscaled per-row derivatives
+              d scores[i] / d X[:, i, :] and d scores[i] / d Y[i, :], which are kept; order and the weights W [d, d] (or None)
+              are constants
+    backward: those times the incoming [n] vector"""
+
+    @staticmethod
+    def forward(ctx, order, W, X, Y):
+        X, Y = X.detach(), Y.detach()
+        scores = torch.empty(X.shape[1], dtype=torch.float64, device=X.device)
+        gx = torch.empty_like(X) if ctx.needs_input_grad[2] else None
+        gy = torch.empty_like(Y) if ctx.needs_input_grad[3] else None
+        ws = torch.empty(_lib.variogram_grad_workspace_bytes(X.shape[1], X.shape[0], X.shape[2]), dtype=torch.uint8,
+                         device=X.device)
+        _lib.variogram_grad(X, Y, W, order, scores, gx, gy, ws)
+        ctx.save_for_backward(gx, gy)
+        return scores
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gS):
+        gx, gy = ctx.saved_tensors
+        return (None, None, gx * gS[None, :, None] if ctx.needs_input_grad[2] else None,
+                gy * gS[:, None] if ctx.needs_input_grad[3] else None)
 
 
 def _gammas(bandwidth):
@@ -414,9 +449,10 @@ def _check_nd(A, name, rank, what):
     return A, tuple(shape)
 
 
-def _score_inputs(X_draws, Y, fair, reduction, per_feature):
-    """the checks, all before a device is touched -> (X [K, n, d], Y [n, d], Y's shape as given): contiguous float64 tensors on one
-    HIP device, in their autograd graph; per_feature: every (row, feature) series becomes a row of one feature"""
+def _score_inputs(X_draws, Y, fair, reduction, per_feature, weights=None, max_d=None):
+    """the checks, all before a device is touched -> (X [K, n, d], Y [n, d], Y's shape as given, weights): contiguous float64
+    tensors on one HIP device, in their autograd graph; per_feature: every (row, feature) series becomes a row of one feature;
+    weights: None or a real [d, d] constant, which comes back detached on the device; max_d: the most features taken"""
     _m1d.check_bool(fair, "fair")
     if reduction not in ("mean", "none"):
         raise ValueError("reduction must be 'mean' or 'none', got %r" % (reduction,))
@@ -432,8 +468,17 @@ def _score_inputs(X_draws, Y, fair, reduction, per_feature):
     if K > _lib.SCORE_MAX_K or K * d > _lib.SCORE_MAX_KD:
         raise ValueError("at most %d draws per row and %d draws times features, got K = %d, d = %d"
                          % (_lib.SCORE_MAX_K, _lib.SCORE_MAX_KD, K, d))
+    if max_d is not None and d > max_d:
+        raise ValueError("at most %d features, got %d" % (max_d, d))
     if n >= 2 ** 31:
         raise ValueError("at most 2**31 - 1 rows, got %d" % n)
+    if weights is not None:
+        try:
+            weights, sw = _check_nd(weights, "weights", 2, "[n_features, n_features]")
+        except (TypeError, ValueError) as e:
+            raise ValueError("weights: expected None or a real numeric array of shape (%d, %d): %s" % (d, d, e)) from None
+        if sw != (d, d):
+            raise ValueError("weights: expected shape (%d, %d), got %s" % (d, d, sw))
     if not torch.cuda.is_available():
         raise RuntimeError("probaforms_amd.metrics runs on a HIP device and none is visible (there is no CPU fallback)")
     dev = next((t.device for t in (X, Yt) if isinstance(t, torch.Tensor) and t.is_cuda),
@@ -443,11 +488,11 @@ def _score_inputs(X_draws, Y, fair, reduction, per_feature):
         if not isinstance(t, torch.Tensor):
             t = torch.from_numpy(np.array(t, dtype=np.float64))                      # (a copy: the caller's may be read-only)
         return t.to(device=dev, dtype=torch.float64).contiguous().reshape(shape)        # torch ops: the graph carries them
-    return dev64(X, (K, n, d)), dev64(Yt, (n, d)), sy
+    return dev64(X, (K, n, d)), dev64(Yt, (n, d)), sy, None if weights is None else dev64(weights, (d, d)).detach()
 
 
 def _score_loss(X_draws, Y, fair, reduction, per_feature):
-    X, Yt, shape = _score_inputs(X_draws, Y, fair, reduction, per_feature)
+    X, Yt, shape, _ = _score_inputs(X_draws, Y, fair, reduction, per_feature)
     with torch.cuda.device(X.device):
         scores = ScoreFunction.apply(bool(fair), X, Yt)
         if reduction == "mean":
@@ -507,3 +552,53 @@ def crps_loss(X_draws, Y, fair=True, reduction="mean"):
     float64 tensor on the device, as energy_score_loss.
     '''
     return _score_loss(X_draws, Y, fair, reduction, True)
+
+
+def _variogram_order(order):
+    number = isinstance(order, (int, float, np.integer, np.floating)) and not isinstance(order, (bool, np.bool_))
+    if not number or float(order) not in (0.5, 1.0, 2.0):
+        raise ValueError("order must be 0.5, 1 or 2, got %r" % (order,))
+    return float(order)
+
+
+def variogram_score_loss(X_draws, Y, order=0.5, weights=None, reduction="mean"):
+    '''
+    The variogram score (Scheuerer & Hamill 2015) of K draws per condition row against the row's observed target, as a
+    differentiable loss: per row VS = sum_i sum_j w_ij (|y_i - y_j|^p - (1/K) sum_k |x_ki - x_kj|^p)^2, with unit weights the
+    `variogram` of sample_joint_scores. It reacts to the dependence between the features, which the energy score hardly sees and
+    the CRPS not at all; it does not see a shift of all features by one constant, so it is trained together with a proper score:
+    energy_score_loss(X_draws, Y) + lam * variogram_score_loss(X_draws, Y).
+
+    Parameters:
+    -----------
+    X_draws: array of shape [n_draws, n_samples, n_features] (numpy, array-like or torch; a CUDA tensor stays on the device)
+        Draw k of row i is X_draws[k, i], as for energy_score_loss. At most 1024 draws, 16384 draws times features and 64 features;
+        one draw is valid.
+    Y: array of shape [n_samples, n_features]
+        The observed targets.
+    order: 0.5, 1 or 2 (int or float)
+        The order p of the variogram. Default = 0.5, as sample_joint_scores. For p = 0.5 the derivative by a coordinate of a
+        draw is sgn(t) / (2 sqrt|t|) of its differences t to the draw's other coordinates: it GROWS WITHOUT BOUND as two
+        coordinates of a draw approach each other (and is taken as 0 where they are equal).
+    weights: None, or an array or tensor of shape [n_features, n_features]
+        w_ij, used as given: it need not be symmetric and may hold negative values. Default = None: all 1. The weights are
+        constants: no gradient flows to them.
+    reduction: "mean" or "none"
+        "mean": the mean over the rows, a 0-d tensor. "none": the [n_samples] per-row scores, for a weighted sum. Default =
+        "mean".
+
+    Return:
+    -------
+    float64 tensor on the device. backward() fills the gradients of whichever of X_draws and Y require one (float32 inputs get
+    float32 gradients); with none only the scores are formed and the result has no grad_fn. A tied pair of coordinates adds the
+    subgradient 0; with one feature the score and both gradients are 0. The contents are not checked: a NaN in a row's draws or
+    target makes that row's score and gradients NaN and touches no other row. With device tensors nothing waits for the device.
+
+    Raises ValueError for an order other than 0.5, 1 or 2, for weights of another shape or dtype, and beyond the limits (there is
+    no fallback).
+    '''
+    order = _variogram_order(order)
+    X, Yt, _, W = _score_inputs(X_draws, Y, False, reduction, False, weights=weights, max_d=_lib.VARIO_MAX_D)
+    with torch.cuda.device(X.device):
+        scores = VariogramFunction.apply(order, W, X, Yt)
+        return scores.mean() if reduction == "mean" else scores
