@@ -122,6 +122,7 @@ __device__ __forceinline__ gw_ptr sbase_w(const float *p) {
     return (gw_ptr)p;
 }
 __device__ __forceinline__ f4 gl_w4(gw_ptr base, unsigned off) { return *reinterpret_cast<const __attribute__((address_space(1))) f4 *>(base + off); }
+__device__ __forceinline__ f2 gl_w2(gw_ptr base, unsigned off) { return *reinterpret_cast<const __attribute__((address_space(1))) f2 *>(base + off); }
 // an LDS position as an opaque 32-bit address: what is added to it later stays an immediate of the DS instruction instead of
 // being folded with the constants already inside the pointer (which pushes paired reads past their 8-bit offset fields)
 typedef __attribute__((address_space(3))) float *lds_ptr;

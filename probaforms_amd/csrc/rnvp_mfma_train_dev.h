@@ -340,6 +340,12 @@ __device__ __forceinline__ void layer_bwd(const float *__restrict__ W, const Geo
         const float *uA2T = W + g.oA2T + (size_t)net * HT * OTL * 256, *uA1T = W + (X4 ? g.oA1X : g.oA1T) + (size_t)net * HT * NGI * 256;
         const unsigned lo4 = lane * 4, qo4 = q * 4;
         f4 a1[K4], a2t[OTL], a1t[NGI], b1;
+        // SB: of a W2^T fragment only this net's two columns (a wave runs one net), as one 64-bit load -- the other half would be
+        // dead registers that the tile body reuses as temporaries, and a load still in flight into them makes it wait
+        auto ld_a2t = [&](gw_ptr base) {
+            const f2 h = gl_w2(base, lo4 + 2 * net);
+            a2t[0][2 * net] = h[0]; a2t[0][2 * net + 1] = h[1];
+        };
         bool have = false;
         if constexpr (SB) {
             have = true;
@@ -348,8 +354,7 @@ __device__ __forceinline__ void layer_bwd(const float *__restrict__ W, const Geo
 #pragma unroll
             for (int k4 = 0; k4 < K4; ++k4) a1[k4] = gl_w4(s1, lo4 + k4 * 256);
             b1 = gl_w4(sb, qo4);
-#pragma unroll
-            for (int o = 0; o < OTL; ++o) a2t[o] = gl_w4(s2, lo4 + o * 256);
+            ld_a2t(s2);
 #pragma unroll
             for (int m = 0; m < NGI; ++m) a1t[m] = gl_w4(s3, lo4 + m * 256);
         }
@@ -376,24 +381,20 @@ __device__ __forceinline__ void layer_bwd(const float *__restrict__ W, const Geo
         }
         for (int ht = ht_lo; ht < ht_hi; ++ht) {
             const int nx = (kAblate & 64) ? 0 : ((ht + 1 < ht_hi) ? ht + 1 : ht);
-            // The next tile's weight fragments.  d <= 16: a second register set, requested here, a whole iteration ahead, and
-            // copied over at the loop's end.  Wider rows (INPL): loaded IN PLACE right after their last use in this tile (a1 / b1 /
-            // a2t after phase 1 of the last row-tile half, a1t after its phase 3) -- half an iteration of cover is enough for the
-            // L2-resident fragments, and the 20-36 registers and 10-18 copies per tile buy more than the distance: round 6, same
-            // box, 65 536 rows: C3 1.188 -> 1.170 ms, C4 1.067 -> 1.032; C2 0.2674 -> 0.2681 (hence not there)
-            // (profiles/r06_bwd_inplace_ab.txt)
-            constexpr bool INPL = NF >= 4;
+            // The next tile's weight fragments.  d <= 16 without net split: a second register set, requested here, a whole iteration
+            // ahead, and copied over at the loop's end.  Wider rows and the d <= 16 net-split launches (INPL): loaded IN PLACE right
+            // after their last use in this tile (a1 / b1 / a2t after phase 1 of the last row-tile half, a1t after its phase 3) --
+            // half an iteration of cover is enough for the L2-resident fragments, and the 20-36 registers and 10-18 copies per tile
+            // buy more than the distance: round 6, same box, 65 536 rows: C3 1.188 -> 1.170 ms, C4 1.067 -> 1.032; C2 0.2674 ->
+            // 0.2681 then (profiles/r06_bwd_inplace_ab.txt).  The net-split form (SB, scalar bases n1 .. n3) gains since its tile body
+            // is issue bound: with ld_a2t's half fragment no load in flight blocks a register the body reuses, and the call falls
+            // 0.2475 -> 0.2438 ms at 65 536 rows, 0.1523 -> 0.1506 at 16 960 (profiles/r31_train_roles_ab.txt)
+            constexpr bool INPL = NF >= 4 || SB;
             f4 na1[K4], na2t[OTL], na1t[NGI], nb1;
+            gw_ptr n1 = nullptr, nb = nullptr, n2 = nullptr, n3 = nullptr;       // SB: the next tile's scalar bases
             if constexpr (SB) {
-                const gw_ptr s1 = sbase_w(uA1 + (size_t)nx * K4 * 256), sb = sbase_w(uB1 + nx * 16);
-                const gw_ptr s2 = sbase_w(uA2T + (size_t)nx * OTL * 256), s3 = sbase_w(uA1T + (size_t)nx * NGI * 256);
-#pragma unroll
-                for (int k4 = 0; k4 < K4; ++k4) na1[k4] = gl_w4(s1, lo4 + k4 * 256);
-                nb1 = gl_w4(sb, qo4);
-#pragma unroll
-                for (int o = 0; o < OTL; ++o) na2t[o] = gl_w4(s2, lo4 + o * 256);
-#pragma unroll
-                for (int m = 0; m < NGI; ++m) na1t[m] = gl_w4(s3, lo4 + m * 256);
+                n1 = sbase_w(uA1 + (size_t)nx * K4 * 256); nb = sbase_w(uB1 + nx * 16);
+                n2 = sbase_w(uA2T + (size_t)nx * OTL * 256); n3 = sbase_w(uA1T + (size_t)nx * NGI * 256);
             } else if constexpr (!INPL) {
 #pragma unroll
                 for (int k4 = 0; k4 < K4; ++k4) na1[k4] = *opaque(pA1 + ((size_t)nx * K4 + k4) * 256);
@@ -439,7 +440,14 @@ __device__ __forceinline__ void layer_bwd(const float *__restrict__ W, const Geo
                         for (int u = 0; u < RH; ++u)
                             gh[u] = mfma16(a2t[0][2 * net + v], go[r0 + u][0][2 * net + v], gh[u]);
                 }
-                if constexpr (INPL) {
+                if constexpr (SB) {
+                    if (r0 + RH >= R) {
+#pragma unroll
+                        for (int k4 = 0; k4 < K4; ++k4) a1[k4] = gl_w4(n1, lo4 + k4 * 256);
+                        b1 = gl_w4(nb, qo4);
+                        ld_a2t(n2);
+                    }
+                } else if constexpr (INPL) {
                     if (r0 + RH >= R) {
 #pragma unroll
                         for (int k4 = 0; k4 < K4; ++k4) a1[k4] = *opaque(pA1 + ((size_t)nx * K4 + k4) * 256);
@@ -513,7 +521,12 @@ __device__ __forceinline__ void layer_bwd(const float *__restrict__ W, const Geo
                             for (int u = 0; u < RH; ++u)
                                 gin[r0 + u][m] = mfma16(a1t[m][rho], gpv[u][rho], gin[r0 + u][m]);
                 }
-                if constexpr (INPL) {
+                if constexpr (SB) {
+                    if (r0 + RH >= R) {
+#pragma unroll
+                        for (int m = 0; m < NGI; ++m) a1t[m] = gl_w4(n3, lo4 + m * 256);
+                    }
+                } else if constexpr (INPL) {
                     if (r0 + RH >= R) {
 #pragma unroll
                         for (int m = 0; m < NGI; ++m) a1t[m] = *opaque(pA1T + ((size_t)nx * NGI + m) * 256);
