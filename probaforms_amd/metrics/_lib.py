@@ -28,6 +28,8 @@ SLICE_LDS_ROWS = 13312     # PFM_SLICE_LDS_ROWS: rows per sample pfm_slice_grad 
 SCORE_MAX_K = 1024         # PFM_SCORE_MAX_K: draws per row of pfm_score_grad
 SCORE_MAX_KD = 16384       # PFM_SCORE_MAX_KD: draws times features of pfm_score_grad (a row's draws in LDS)
 VARIO_MAX_D = 64           # PFM_VARIO_MAX_D: features of pfm_variogram_grad (a row's pair table in LDS beside its draws)
+SORT_MAX_K = 8192          # PFM_SORT_MAX_K: draws per series of pfm_sort_score (a series' entries and ranks in the LDS of one CU)
+SORT_MAX_Q = 16            # PFM_SORT_MAX_Q: quantile levels of pfm_sort_score and pfm_pinball_grad
 PFM_EINVAL, PFM_EUNSUPPORTED, PFM_EWORKSPACE = -1, -2, -3
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -75,6 +77,10 @@ _SIGNATURES = {
     "pfm_variogram_grad_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
     "pfm_variogram_plan": (C.c_int, [_I64, _I64, _I64, _VP]),
     "pfm_variogram_grad": (C.c_int, [_VP, _VP, _VP, _VP, _I64, _I64, _I64, C.c_double, _VP, _VP, _VP, _VP, _SZ]),
+    "pfm_sort_score_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
+    "pfm_sort_score_plan": (C.c_int, [_I64, _I64, _VP]),
+    "pfm_sort_score": (C.c_int, [_VP, _VP, _VP, _I64, _I64, C.c_int, _VP, C.c_int, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _SZ]),
+    "pfm_pinball_grad": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int, _I64, _I64, _VP, _VP, _VP, _SZ]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -465,3 +471,70 @@ def variogram_grad_status(X, Y, W, order, scores, grad_x, grad_y, ws):
 
 def variogram_grad(*args):
     check(variogram_grad_status(*args), "pfm_variogram_grad")
+
+
+def sort_score_workspace_bytes(M, K, n_levels=0):
+    return int(lib().pfm_sort_score_workspace_bytes(int(M), int(K), int(n_levels)))
+
+
+def sort_score_plan_status(M, K):
+    """-> (status, (series per workgroup, pitch of a series in LDS, LDS bytes, workgroups)): how pfm_sort_score tiles a call; no
+    device is touched"""
+    plan = (C.c_int64 * 4)()
+    st = int(lib().pfm_sort_score_plan(int(M), int(K), C.cast(plan, _VP)))
+    return st, tuple(int(v) for v in plan)
+
+
+def sort_score_plan(M, K):
+    st, plan = sort_score_plan_status(M, K)
+    check(st, "pfm_sort_score_plan")
+    return plan
+
+
+def _levels(levels):
+    """a sequence of Python floats as the HOST array of the C call (read before it returns) -> (pointer or None, count, keep-alive)"""
+    arr = (C.c_double * max(1, len(levels)))(*[float(v) for v in levels])
+    return (C.cast(arr, _VP) if len(levels) else None), len(levels), arr
+
+
+def sort_score_status(X, Y, fair, levels, crps, grad_x, grad_y, pinball, side, idx, ws):
+    """enqueue, from the sorted series of the draws X [K, M] against the targets Y [M], whichever are given of the CRPS [M], its
+    derivatives grad_x [K, M] and grad_y [M], and for the sequence `levels` of Q Python floats the pinball scores [Q, M], side [Q, M]
+    and idx [Q, M, 2] (int32) on the current stream and return the status"""
+    K, M = X.shape
+    Q = len(levels)
+    assert Y.numel() == M and (crps is None or crps.numel() == M) and (grad_y is None or grad_y.numel() == M)
+    assert grad_x is None or tuple(grad_x.shape) == (K, M)
+    assert all(t is None or t.numel() == Q * M for t in (pinball, side)) and (idx is None or idx.numel() == 2 * Q * M)
+    lp, Q, keep = _levels(levels)
+    return int(lib().pfm_sort_score(torch.cuda.current_stream().cuda_stream, _ptr(X, torch.float64, "X_draws"),
+                                    _ptr(Y, torch.float64, "Y"), M, K, int(bool(fair)), lp, Q,
+                                    _ptr(crps, torch.float64, "crps", nullable=True),
+                                    _ptr(grad_x, torch.float64, "grad_x", nullable=True),
+                                    _ptr(grad_y, torch.float64, "grad_y", nullable=True),
+                                    _ptr(pinball, torch.float64, "pinball", nullable=True),
+                                    _ptr(side, torch.float64, "side", nullable=True), _ptr(idx, torch.int32, "idx", nullable=True),
+                                    _ptr(ws, torch.uint8, "workspace"), ws.numel()))
+
+
+def sort_score(*args):
+    check(sort_score_status(*args), "pfm_sort_score")
+
+
+def pinball_grad_status(idx, side, g, levels, K, grad_x, grad_y, ws):
+    """enqueue the derivatives of sum g * pinball by the draws, grad_x [K, M], and by the targets, grad_y [M] (either may be None),
+    from pfm_sort_score's idx [Q, M, 2] and side [Q, M], the incoming g [Q, M] and the same `levels`, on the current stream and
+    return the status"""
+    Q, M = side.shape
+    assert len(levels) == Q and tuple(g.shape) == (Q, M) and idx.numel() == 2 * Q * M
+    assert (grad_x is None or tuple(grad_x.shape) == (K, M)) and (grad_y is None or grad_y.numel() == M)
+    lp, Q, keep = _levels(levels)
+    return int(lib().pfm_pinball_grad(torch.cuda.current_stream().cuda_stream, _ptr(idx, torch.int32, "idx"),
+                                      _ptr(side, torch.float64, "side"), _ptr(g, torch.float64, "g"), lp, Q, M, int(K),
+                                      _ptr(grad_x, torch.float64, "grad_x", nullable=True),
+                                      _ptr(grad_y, torch.float64, "grad_y", nullable=True), _ptr(ws, torch.uint8, "workspace"),
+                                      ws.numel()))
+
+
+def pinball_grad(*args):
+    check(pinball_grad_status(*args), "pfm_pinball_grad")

@@ -45,9 +45,16 @@
  *   pfm_variogram_grad per row, the variogram score of the row's K draws against the row's target TOGETHER WITH its derivative by
  *                     every draw and by the target: the score that reacts to the dependence between the features; a row's
  *                     d (d - 1) / 2 pair terms stay in LDS; pfm_variogram_plan says how a shape is tiled
+ *   pfm_sort_score    per (row, feature) series, the CRPS of the series' K draws against its target TOGETHER WITH its derivative
+ *                     by every draw and by the target, and the pinball scores of the draws' empirical quantiles: a (value, draw)
+ *                     sort of the series in LDS and one pass, O(K log^2 K) where pfm_score_grad walks K^2 / 2 pairs;
+ *                     pfm_sort_score_plan says how a shape is tiled
+ *   pfm_pinball_grad  the derivative of those pinball scores by every draw and by the target, from the two order statistics
+ *                     pfm_sort_score names per level
  *
  * Conventions (as include/rnvp_hip.h)
- *   - every pointer is a DEVICE pointer (but pfm_pair_grad's `gammas`); sizes are plain integers;
+ *   - every pointer is a DEVICE pointer (but pfm_pair_grad's `gammas` and the `levels` of pfm_sort_score and
+ *     pfm_pinball_grad); sizes are plain integers;
  *   - the caller owns all device memory including the workspace (no hidden hipMalloc);
  *     *_workspace_bytes() says how much a call needs;
  *   - kernels are enqueued on `stream` (a hipStream_t passed as void*) and the call
@@ -481,6 +488,77 @@ int pfm_variogram_plan(int64_t n, int64_t K, int64_t d, int64_t *plan);
  */
 int pfm_variogram_grad(void *stream, const double *X, const double *Y, const double *W, int64_t n, int64_t K, int64_t d,
                        double order, double *scores, double *grad_x, double *grad_y, void *workspace, size_t workspace_bytes);
+
+/* ---- differentiable per-series scoring rules from the sorted draws: CRPS and pinball (pf_sortscore.hip) ---- */
+
+#define PFM_SORT_MAX_K 8192         /* draws per series of pfm_sort_score: a series' (value, draw) pairs and ranks in the LDS of one CU */
+#define PFM_SORT_MAX_Q 16           /* quantile levels of pfm_sort_score and pfm_pinball_grad: they travel as kernel arguments */
+
+/* bytes of workspace pfm_sort_score and pfm_pinball_grad need: nothing is kept there, the figure is the least a caller can
+   allocate (0: the arguments are invalid or outside the limits) */
+size_t pfm_sort_score_workspace_bytes(int64_t M, int64_t K, int64_t n_levels);
+
+/*
+ * How pfm_sort_score tiles a call of M series of K draws; needs no device.  plan is a HOST array of 4:
+ *   plan[0]  G: the consecutive series a workgroup stages and sorts at once (for every draw, one contiguous run of G doubles
+ *            of X and of grad_x): 3776 / pitch, at least 1
+ *   plan[1]  the pitch: doubles between two series in LDS, K | 1: odd, so that staging a draw's run (stride = pitch) and a
+ *            lane per series meet every bank once
+ *   plan[2]  the dynamic LDS bytes of a workgroup, at most 163840: 16 per entry (float64 value, int32 draw, two int16 ranks)
+ *            and the sums' scratch
+ *   plan[3]  the workgroups, ceil(M / G)
+ * Only plan[3] depends on M; no output of pfm_sort_score depends on any of them.
+ * The statuses are pfm_sort_score's for the sizes; PFM_EINVAL for a NULL plan.
+ */
+int pfm_sort_score_plan(int64_t M, int64_t K, int64_t *plan);
+
+/*
+ * The CRPS of every series' K draws against the series' target with its derivatives, and the pinball scores of the draws'
+ * empirical quantiles, from the sorted series.  X [K, M] holds draw k of series s at X[k, s] (a [K, n, d] array of draws is M = n d
+ * series as it lies), Y [M] the targets.  Per series the shifted draws t_k = x_k - y are sorted by (value, draw index); t_(i) is
+ * the i-th of them, lo_i and hi_i the first and the last sorted position of the run of values equal (==) to t_(i), and
+ *   c_i = lo_i + hi_i - K + 1 = #{draws below t_(i)} - #{draws above it}                 (2 i - K + 1 without ties)
+ * With D = K - 1 if fair else K:
+ *   crps[s]      = (1 / K) sum_i |t_(i)| - (1 / (K D)) sum_i c_i t_(i)
+ *   grad_x[k, s] = (sgn(t_k) D - c_k) / (K D)          = d crps[s] / d X[k, s]: an integer over an integer, one division
+ *   grad_y[s]    = -(sum_k sgn(t_k)) / K               = d crps[s] / d Y[s]
+ * sgn(0) = 0: tied draws and a draw on its target get the subgradient pfm_score_grad gives them at d = 1.  The two routes agree to
+ * rounding, not bitwise: their sums run in different orders.  A series whose sum of |t| is NaN (a NaN among its draws or in its
+ * target) gets NaN for its score and for every element of its gradients; infinities are not treated, they stay in their series.
+ * levels is a HOST array of n_levels probabilities in [0, 1] (n_levels <= PFM_SORT_MAX_Q; 0: no quantile output), read before the
+ * call returns.  Per level p: h = p (K - 1), i = floor(h) clipped to K - 2 (0 at K = 1), frac = h - i, and
+ *   Q_p - y         = lerp(t_(i), t_(i + 1), frac)     numpy's: a + (b - a) frac; b - (b - a) (1 - frac) for frac >= 0.5; a if b == a
+ *   side[q, s]      = p - [y < Q_p]
+ *   pinball[q, s]   = (y - Q_p) side[q, s]
+ *   idx[q, s, 0..1] = the draws (their k) that are t_(i) and t_(i + 1); the same draw twice at K = 1
+ * pinball and side are NaN for a series that holds a NaN; its idx are two of its draws.
+ * crps [M], grad_x [K, M], grad_y [M], pinball [n_levels, M], side [n_levels, M] and idx [n_levels, M, 2] (int32) may each be NULL.
+ * No float atomics, and nothing is kept in the workspace; the order of every sum depends on K only and a series never meets
+ * another: its outputs are bitwise the same at any position, for any M, in any call, whichever outputs are asked for.  On success
+ * every element of every output given is written.
+ * PFM_EINVAL for M or K < 1, M >= 2^31, fair != 0 with K = 1, n_levels < 0, a level outside [0, 1] or NaN, a NULL X or Y, NULL levels
+ * with n_levels > 0, pinball, side or idx given with n_levels = 0, or no output at all; PFM_EUNSUPPORTED for K > PFM_SORT_MAX_K or
+ * n_levels > PFM_SORT_MAX_Q; PFM_EWORKSPACE for a missing or short workspace; on any error nothing is written.
+ */
+int pfm_sort_score(void *stream, const double *X, const double *Y, int64_t M, int64_t K, int fair, const double *levels,
+                   int n_levels, double *crps, double *grad_x, double *grad_y, double *pinball, double *side, int32_t *idx,
+                   void *workspace, size_t workspace_bytes);
+
+/*
+ * The derivatives of sum_q sum_s g[q, s] pinball[q, s] by the draws and by the targets, from what pfm_sort_score left: idx
+ * [n_levels, M, 2] and side [n_levels, M]; g [n_levels, M] is the incoming weight, levels the HOST array of that call (frac is
+ * formed from it as there), read before the call returns.  With w = g[q, s] side[q, s]:
+ *   grad_x[idx[q, s, 0], s] += (-w) (1 - frac_q),   grad_x[idx[q, s, 1], s] += (-w) frac_q       for q ascending
+ *   grad_y[s]                = sum_q w                                                          for q ascending
+ * grad_x [K, M] is zero-filled on `stream` first; one thread owns a series, so two levels that meet on one order statistic add in a
+ * fixed order.  An idx outside [0, K) is clamped into it.  grad_x and grad_y may each be NULL, not both; every element of every
+ * output given is written.  A series that holds a NaN has a NaN side: its grad_y and the two draws named per level get NaN.
+ * PFM_EINVAL for M or K < 1, M >= 2^31, n_levels < 1, a level outside [0, 1] or NaN, a NULL idx, side, g or levels, or no output at
+ * all; PFM_EUNSUPPORTED for K > PFM_SORT_MAX_K or n_levels > PFM_SORT_MAX_Q; PFM_EWORKSPACE for a missing or short workspace; on any
+ * error nothing is written.
+ */
+int pfm_pinball_grad(void *stream, const int32_t *idx, const double *side, const double *g, const double *levels, int n_levels,
+                     int64_t M, int64_t K, double *grad_x, double *grad_y, void *workspace, size_t workspace_bytes);
 
 /* ---- nearest-neighbour two-sample test (pf_nn.hip) ------------------------------------------------ */
 

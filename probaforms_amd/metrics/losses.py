@@ -46,6 +46,11 @@ with a backward().  The energy score hardly separates predictive laws that diffe
 the CRPS is blind to it; the variogram score reacts to it, and is trained as energy_score_loss + lambda * variogram_score_loss.  A
 row's d (d - 1) / 2 pair terms stay in LDS beside its draws: nothing of size K d^2 or n d^2 is stored, for the forward or for the
 backward.
+
+crps_loss(method="sorted") and pinball_loss are the sort-based conditional members (kernels: csrc/pf_sortscore.hip, pfm_sort_score
+and pfm_pinball_grad): every (row, feature) series of draws is sorted by (value, draw) in LDS and scored in one pass, O(K log^2 K)
+per series where the pair walk costs K^2 / 2, for up to 8192 draws.  Once the series is sorted the derivative of the CRPS by a draw is
+a ratio of integers taken from the draw's rank, and the derivative of an empirical quantile touches two order statistics.
 """
 import math
 
@@ -186,6 +191,67 @@ class VariogramFunction(torch.autograd.Function):
         gx, gy = ctx.saved_tensors
         return (None, None, gx * gS[None, :, None] if ctx.needs_input_grad[2] else None,
                 gy * gS[:, None] if ctx.needs_input_grad[3] else None)
+
+
+class SortedCrpsFunction(torch.autograd.Function):
+    """The CRPS [M] of the draws X [K, M] against the targets Y [M] from the sorted series, as one autograd node.
+
+    forward : pfm_sort_score once: the scores and, for whichever of X and Y requires a gradient, the unscaled derivatives
+              d crps[s] / d X[:, s] and d crps[s] / d Y[s], which are kept
+    backward: those times the incoming [M] vector"""
+
+    @staticmethod
+    def forward(ctx, fair, X, Y):
+        X, Y = X.detach(), Y.detach()
+        scores = torch.empty(X.shape[1], dtype=torch.float64, device=X.device)
+        gx = torch.empty_like(X) if ctx.needs_input_grad[1] else None
+        gy = torch.empty_like(Y) if ctx.needs_input_grad[2] else None
+        ws = torch.empty(_lib.sort_score_workspace_bytes(X.shape[1], X.shape[0]), dtype=torch.uint8, device=X.device)
+        _lib.sort_score(X, Y, fair, (), scores, gx, gy, None, None, None, ws)
+        ctx.save_for_backward(gx, gy)
+        return scores
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gS):
+        gx, gy = ctx.saved_tensors
+        return None, gx * gS[None, :] if ctx.needs_input_grad[1] else None, gy * gS if ctx.needs_input_grad[2] else None
+
+
+class PinballFunction(torch.autograd.Function):
+    """The pinball scores [Q, M] of the empirical quantiles of the draws X [K, M] at the levels (a tuple of Q floats, constants)
+    against the targets Y [M], as one autograd node.
+
+    forward : pfm_sort_score once: the scores and, if X or Y requires a gradient, per level and series the two draws the quantile
+              lies between (idx) and side = p - [y < Q_p], which are kept: 2 Q M numbers, not K M
+    backward: pfm_pinball_grad once: the incoming [Q, M] weights go to those two draws and to the target"""
+
+    @staticmethod
+    def forward(ctx, levels, X, Y):
+        X, Y = X.detach(), Y.detach()
+        K, M = X.shape
+        Q = len(levels)
+        want = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        pin = torch.empty((Q, M), dtype=torch.float64, device=X.device)
+        side = torch.empty_like(pin) if want else None
+        idx = torch.empty((Q, M, 2), dtype=torch.int32, device=X.device) if want else None
+        ws = torch.empty(_lib.sort_score_workspace_bytes(M, K, Q), dtype=torch.uint8, device=X.device)
+        _lib.sort_score(X, Y, False, levels, None, None, None, pin, side, idx, ws)
+        ctx.levels, ctx.K = levels, K
+        ctx.save_for_backward(idx, side)
+        return pin
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gP):
+        idx, side = ctx.saved_tensors
+        Q, M = side.shape
+        gx = torch.empty((ctx.K, M), dtype=torch.float64, device=side.device) if ctx.needs_input_grad[1] else None
+        gy = torch.empty(M, dtype=torch.float64, device=side.device) if ctx.needs_input_grad[2] else None
+        ws = torch.empty(_lib.sort_score_workspace_bytes(M, ctx.K, Q), dtype=torch.uint8, device=side.device)
+        with torch.cuda.device(side.device):
+            _lib.pinball_grad(idx, side, gP.contiguous(), ctx.levels, ctx.K, gx, gy, ws)
+        return None, gx, gy
 
 
 def _gammas(bandwidth):
@@ -449,10 +515,11 @@ def _check_nd(A, name, rank, what):
     return A, tuple(shape)
 
 
-def _score_inputs(X_draws, Y, fair, reduction, per_feature, weights=None, max_d=None):
+def _score_inputs(X_draws, Y, fair, reduction, per_feature, weights=None, max_d=None, sort_route=False):
     """the checks, all before a device is touched -> (X [K, n, d], Y [n, d], Y's shape as given, weights): contiguous float64
     tensors on one HIP device, in their autograd graph; per_feature: every (row, feature) series becomes a row of one feature;
-    weights: None or a real [d, d] constant, which comes back detached on the device; max_d: the most features taken"""
+    weights: None or a real [d, d] constant, which comes back detached on the device; max_d: the most features taken; sort_route:
+    the limits are pfm_sort_score's, not pfm_score_grad's"""
     _m1d.check_bool(fair, "fair")
     if reduction not in ("mean", "none"):
         raise ValueError("reduction must be 'mean' or 'none', got %r" % (reduction,))
@@ -465,7 +532,10 @@ def _score_inputs(X_draws, Y, fair, reduction, per_feature, weights=None, max_d=
         n, d = n * d, 1
     if fair and K == 1:
         raise ValueError("fair=True needs at least 2 draws per row (the spread is divided by K - 1), got 1")
-    if K > _lib.SCORE_MAX_K or K * d > _lib.SCORE_MAX_KD:
+    if sort_route:
+        if K > _lib.SORT_MAX_K:
+            raise ValueError("at most %d draws per series, got %d" % (_lib.SORT_MAX_K, K))
+    elif K > _lib.SCORE_MAX_K or K * d > _lib.SCORE_MAX_KD:
         raise ValueError("at most %d draws per row and %d draws times features, got K = %d, d = %d"
                          % (_lib.SCORE_MAX_K, _lib.SCORE_MAX_KD, K, d))
     if max_d is not None and d > max_d:
@@ -532,26 +602,100 @@ def energy_score_loss(X_draws, Y, fair=True, reduction="mean"):
     return _score_loss(X_draws, Y, fair, reduction, False)
 
 
-def crps_loss(X_draws, Y, fair=True, reduction="mean"):
+def _sorted_inputs(X_draws, Y, fair, reduction):
+    """_score_inputs for the sorted route -> (X [K, M], Y [M], Y's shape as given): every (row, feature) series is a column"""
+    X, Yt, shape, _ = _score_inputs(X_draws, Y, fair, reduction, True, sort_route=True)
+    return X.reshape(X.shape[0], X.shape[1]), Yt.reshape(-1), shape
+
+
+def crps_loss(X_draws, Y, fair=True, reduction="mean", method="pairs"):
     '''
     The continuous ranked probability score of K draws per condition row and feature against the observed value, as a
     differentiable loss: the energy score of every (row, feature) series on its own, at n_features = 1 the `crps` of
-    sample_scores. The same kernel call as energy_score_loss on X_draws.reshape(K, n d, 1) and Y.reshape(n d, 1).
+    sample_scores.
 
-    It walks the K (K - 1) / 2 pairs of every series, O(K^2). The sorted O(K log K) route of sample_scores has no gradient here;
-    a sorted route with a gradient is not provided.
+    method="pairs" is the same kernel call as energy_score_loss on X_draws.reshape(K, n d, 1) and Y.reshape(n d, 1): it walks the
+    K (K - 1) / 2 pairs of every series, O(K^2), for at most 1024 draws.
+
+    method="sorted" sorts every series by (value, draw) and takes the score and both derivatives from one pass over the sorted
+    series, O(K log^2 K), for at most 8192 draws: with t = x - y sorted, crps = (1/K) sum_i |t_(i)| - 1/(K D) sum_i c_i t_(i) and
+    d crps / d x_k = (sgn(t_k) D - c_k) / (K D), c_i being the number of draws strictly below t_(i) minus the number strictly above
+    (2 i - K + 1 without ties). Tied draws and a draw on its target get the subgradient of the pair route (sgn(0) = 0). The two
+    routes agree to rounding, not bitwise: their sums run in different orders. Nothing switches between them automatically.
 
     Parameters:
     -----------
-    X_draws, Y, fair: as energy_score_loss; at most 1024 draws.
+    X_draws, Y, fair: as energy_score_loss; at most 1024 draws for method="pairs" and 8192 for method="sorted".
     reduction: "mean" or "none"
         "mean": the mean over rows and features, a 0-d tensor. "none": the [n_samples, n_features] scores. Default = "mean".
+    method: "pairs" or "sorted"
+        Default = "pairs".
 
     Return:
     -------
-    float64 tensor on the device, as energy_score_loss.
+    float64 tensor on the device, as energy_score_loss. With method="sorted" a NaN in a series' draws or target makes that
+    series' score and all its gradient elements NaN and touches no other series.
+
+    Raises ValueError for another method and beyond the limits of the method asked for (there is no fallback).
     '''
-    return _score_loss(X_draws, Y, fair, reduction, True)
+    if method == "pairs":
+        return _score_loss(X_draws, Y, fair, reduction, True)
+    if method != "sorted":
+        raise ValueError("method must be 'pairs' or 'sorted', got %r" % (method,))
+    X, Yt, shape = _sorted_inputs(X_draws, Y, fair, reduction)
+    with torch.cuda.device(X.device):
+        scores = SortedCrpsFunction.apply(bool(fair), X, Yt)
+        return scores.mean() if reduction == "mean" else scores.reshape(shape)
+
+
+def _quantile_levels(quantiles):
+    """a number or a sequence of 1 .. 16 of them in [0, 1] -> the tuple of floats"""
+    seq = isinstance(quantiles, (list, tuple)) or (isinstance(quantiles, np.ndarray) and quantiles.ndim == 1)
+    levels = list(quantiles) if seq else [quantiles]
+    if not 1 <= len(levels) <= _lib.SORT_MAX_Q:
+        raise ValueError("quantiles must be a number in [0, 1] or a sequence of 1 to %d of them, got %d values"
+                         % (_lib.SORT_MAX_Q, len(levels)))
+    for p in levels:
+        number = isinstance(p, (int, float, np.integer, np.floating)) and not isinstance(p, (bool, np.bool_))
+        if not number or not 0.0 <= float(p) <= 1.0:
+            raise ValueError("quantiles must be numbers in [0, 1], got %r" % (p,))
+    return tuple(float(p) for p in levels)
+
+
+def pinball_loss(X_draws, Y, quantiles=(0.05, 0.95), reduction="mean"):
+    '''
+    The pinball (quantile) loss of the empirical quantiles of K draws per condition row and feature against the observed value, as a
+    differentiable loss: per level p, (y - Q_p) (p - [y < Q_p]) with Q_p numpy's linear quantile of the series' draws, the `pinball`
+    of sample_scores. It is the quantile-regression loss, and the CRPS is twice its integral over p: training on a few levels
+    fits those quantiles of the sampler, e.g. the 5 % / 95 % band.
+
+    Every series is sorted by (value, draw) as for crps_loss(method="sorted"). Q_p lies between two order statistics, h = p (K - 1),
+    i = floor(h), frac = h - i: the derivative goes to those two draws, -(p - [y < Q_p]) (1 - frac) and -(p - [y < Q_p]) frac, and
+    p - [y < Q_p] to the target. Among tied draws the (value, draw index) order names the two; y on Q_p counts as y >= Q_p.
+
+    Parameters:
+    -----------
+    X_draws, Y: as energy_score_loss; at most 8192 draws, one draw is valid.
+    quantiles: float, or a sequence of 1 to 16 floats in [0, 1]
+        The levels p. Default = (0.05, 0.95). They are constants.
+    reduction: "mean" or "none"
+        "mean": the mean over levels, rows and features, a 0-d tensor. "none": the [n_levels, n_samples, n_features] scores.
+        Default = "mean".
+
+    Return:
+    -------
+    float64 tensor on the device. backward() fills the gradients of whichever of X_draws and Y require one (float32 inputs get
+    float32 gradients); with none only the scores are formed and the result has no grad_fn. The contents are not checked: a NaN
+    in a series' draws or target makes that series' scores NaN and touches no other series. With device tensors nothing waits for
+    the device.
+
+    Raises ValueError for no level, more than 16, a level outside [0, 1], and more than 8192 draws (there is no fallback).
+    '''
+    levels = _quantile_levels(quantiles)
+    X, Yt, shape = _sorted_inputs(X_draws, Y, False, reduction)
+    with torch.cuda.device(X.device):
+        pin = PinballFunction.apply(levels, X, Yt)
+        return pin.mean() if reduction == "mean" else pin.reshape((len(levels),) + shape)
 
 
 def _variogram_order(order):
