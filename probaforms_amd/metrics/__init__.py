@@ -35,6 +35,13 @@ row's own observed target, the energy score and the CRPS that sample_joint_score
 
     from probaforms_amd.metrics.losses import energy_score_loss, crps_loss    # X_draws [K, n, d] against Y [n, d], per row
 
+The Frechet distance has both forms as well, wholly on the device for at most 64 features (a symmetric eigensolver in LDS gives the
+trace of the matrix square root and, being a spectral function, its gradient): moment matching, O(n d^2) where the pair losses
+walk n^2 pairs:
+
+    from probaforms_amd.metrics.fd import frechet_distance_full_sample       # the samples as given, a numpy float
+    from probaforms_amd.metrics.losses import frechet_loss                   # the same value with a backward()
+
 `__all__` and the `probaforms.metrics` alias (`probaforms_amd.install_as_probaforms()`) name only the two
 multivariate metrics, so `from probaforms.metrics import kolmogorov_smirnov_1d` raises ImportError there.
 """

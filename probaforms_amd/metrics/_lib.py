@@ -30,6 +30,8 @@ SCORE_MAX_KD = 16384       # PFM_SCORE_MAX_KD: draws times features of pfm_score
 VARIO_MAX_D = 64           # PFM_VARIO_MAX_D: features of pfm_variogram_grad (a row's pair table in LDS beside its draws)
 SORT_MAX_K = 8192          # PFM_SORT_MAX_K: draws per series of pfm_sort_score (a series' entries and ranks in the LDS of one CU)
 SORT_MAX_Q = 16            # PFM_SORT_MAX_Q: quantile levels of pfm_sort_score and pfm_pinball_grad
+FRECHET_MAX_D = 64         # PFM_FRECHET_MAX_D: rows of a matrix of pfm_sym_eig, features of pfm_frechet_grad (four matrices in LDS)
+EIG_MAX_SWEEPS = 30        # PFM_EIG_MAX_SWEEPS: the sweeps after which pfm_sym_eig stops whatever the matrix holds
 PFM_EINVAL, PFM_EUNSUPPORTED, PFM_EWORKSPACE = -1, -2, -3
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -81,6 +83,10 @@ _SIGNATURES = {
     "pfm_sort_score_plan": (C.c_int, [_I64, _I64, _VP]),
     "pfm_sort_score": (C.c_int, [_VP, _VP, _VP, _I64, _I64, C.c_int, _VP, C.c_int, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _SZ]),
     "pfm_pinball_grad": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int, _I64, _I64, _VP, _VP, _VP, _SZ]),
+    "pfm_sym_eig_workspace_bytes": (_SZ, [_I64, _I64]),
+    "pfm_sym_eig": (C.c_int, [_VP, _VP, _I64, _I64, _VP, _VP, _VP, _VP, _SZ]),
+    "pfm_frechet_grad_workspace_bytes": (_SZ, [_I64, _I64, _I64]),
+    "pfm_frechet_grad": (C.c_int, [_VP, _VP, _I64, _I64, _I64, C.c_double, C.c_int, _VP, _VP, _VP, _VP, _VP, _VP, _SZ]),
 }
 EXPORTS = tuple(_SIGNATURES)
 
@@ -538,3 +544,53 @@ def pinball_grad_status(idx, side, g, levels, K, grad_x, grad_y, ws):
 
 def pinball_grad(*args):
     check(pinball_grad_status(*args), "pfm_pinball_grad")
+
+
+def sym_eig_workspace_bytes(batch, d):
+    return int(lib().pfm_sym_eig_workspace_bytes(int(batch), int(d)))
+
+
+def sym_eig_status(A, w, V, sweeps, ws):
+    """enqueue the eigenvalues w [batch, d] (ascending) and, where given, the eigenvectors V [batch, d, d] (columns) and the sweep
+    counts [batch] (int32) of the symmetric matrices A [batch, d, d] (lower triangles read) on the current stream and return the
+    status"""
+    batch, d, d2 = A.shape
+    assert d == d2 and tuple(w.shape) == (batch, d) and (V is None or tuple(V.shape) == (batch, d, d))
+    assert sweeps is None or sweeps.numel() == batch
+    return int(lib().pfm_sym_eig(torch.cuda.current_stream().cuda_stream, _ptr(A, torch.float64, "A"), batch, d,
+                                 _ptr(w, torch.float64, "w"), _ptr(V, torch.float64, "V", nullable=True),
+                                 _ptr(sweeps, torch.int32, "sweeps", nullable=True), _ptr(ws, torch.uint8, "workspace"), ws.numel()))
+
+
+def sym_eig(*args):
+    check(sym_eig_status(*args), "pfm_sym_eig")
+
+
+def frechet_grad_workspace_bytes(n, d, n_first):
+    return int(lib().pfm_frechet_grad_workspace_bytes(int(n), int(d), int(n_first)))
+
+
+def frechet_moments(ws, d):
+    """the views mean [2, d] and cov [2, d, d] of the moments a pfm_frechet_grad call left in its workspace `ws`"""
+    off = (16 * d + 255) & ~255
+    return ws[:16 * d].view(torch.float64).view(2, d), ws[off:off + 16 * d * d].view(torch.float64).view(2, d, d)
+
+
+def frechet_grad_status(Z, n_first, rcond, sides, value, grad, parts, eig, rank, ws):
+    """enqueue the Frechet distance [1] of the pooled sample Z [n, d] and, where given, its row gradients [n, d] (sides: bit 0 the
+    real rows, bit 1 the fake rows), parts [5], the eigenvalues [d] and the ranks [2] (int32) on the current stream and return the
+    status"""
+    n, d = Z.shape
+    assert value.numel() == 1 and (grad is None or tuple(grad.shape) == (n, d))
+    assert (parts is None or parts.numel() == 5) and (eig is None or eig.numel() == d) and (rank is None or rank.numel() == 2)
+    return int(lib().pfm_frechet_grad(torch.cuda.current_stream().cuda_stream, _ptr(Z, torch.float64, "Z"), n, d, int(n_first),
+                                      float(rcond), int(sides), _ptr(value, torch.float64, "value"),
+                                      _ptr(grad, torch.float64, "grad", nullable=True),
+                                      _ptr(parts, torch.float64, "parts", nullable=True),
+                                      _ptr(eig, torch.float64, "eig", nullable=True),
+                                      _ptr(rank, torch.int32, "rank", nullable=True), _ptr(ws, torch.uint8, "workspace"),
+                                      ws.numel()))
+
+
+def frechet_grad(*args):
+    check(frechet_grad_status(*args), "pfm_frechet_grad")

@@ -7,7 +7,7 @@
  *                     radix select, then the RBF kernel means over XX, YY and XY
  *   pfm_boot_moments  mean and np.cov covariance (ddof 1) of each resampled set
  *                     (probaforms/metrics/fd.py); the trace of the matrix square root is
- *                     left to the caller
+ *                     left to the caller (pfm_frechet_grad forms it on the device)
  *   pfm_metric1d      the per-feature rank and density statistics behind the eight 1-D
  *                     metrics (probaforms/metrics/ks1d.py, div1d.py), from the pooled
  *                     column's sorted order and the replicate's draw counts
@@ -51,6 +51,11 @@
  *                     pfm_sort_score_plan says how a shape is tiled
  *   pfm_pinball_grad  the derivative of those pinball scores by every draw and by the target, from the two order statistics
  *                     pfm_sort_score names per level
+ *   pfm_sym_eig       eigenvalues and eigenvectors of a batch of real symmetric matrices of up to 64 rows: cyclic Jacobi in a
+ *                     parallel order, one workgroup per matrix, the matrix and its eigenvectors in LDS
+ *   pfm_frechet_grad  the Frechet distance of the samples as given, the trace of the matrix square root included, TOGETHER WITH
+ *                     its derivative by every row: the moments of pfm_boot_moments, two eigen-decompositions per route in one
+ *                     workgroup, and one row kernel, O(n d^2); the gradient of a spectral function needs no eigenvector derivative
  *
  * Conventions (as include/rnvp_hip.h)
  *   - every pointer is a DEVICE pointer (but pfm_pair_grad's `gammas` and the `levels` of pfm_sort_score and
@@ -83,7 +88,8 @@ extern "C" {
 #define PFM_EUNSUPPORTED (-2)   /* d too large for the moments kernels' LDS row tile;
                                    a Wasserstein order or Sinkhorn cost power p other than 1 or 2;
                                    nearest_k above PFM_KNN_MAX_K; k above PFM_NN_MAX_K;
-                                   a sample above PFM_SLICE_LDS_ROWS without perm_in      */
+                                   a sample above PFM_SLICE_LDS_ROWS without perm_in;
+                                   d above PFM_FRECHET_MAX_D in pfm_sym_eig, pfm_frechet_grad */
 #define PFM_EWORKSPACE   (-3)   /* workspace smaller than *_workspace_bytes() says      */
 
 #define PFM_VERSION 101         /* pfm_version(): bumped whenever an argument list changes */
@@ -596,6 +602,76 @@ size_t pfm_nn_count_workspace_bytes(int64_t n, int64_t k, int64_t reps);
  */
 int pfm_nn_count(void *stream, const int32_t *nbr, int64_t n, int64_t k, const uint8_t *labels, int64_t reps,
                  int64_t *counts, void *workspace, size_t workspace_bytes);
+
+/* ---- symmetric eigensolver and the differentiable Frechet distance (pf_frechet.hip) ------------------ */
+
+#define PFM_FRECHET_MAX_D 64        /* rows of a matrix of pfm_sym_eig, features of pfm_frechet_grad: four d x d float64 matrices at a
+                                       row pitch of d | 1 fit the 160 KiB of LDS of one CU */
+#define PFM_EIG_MAX_SWEEPS 30       /* sweeps after which pfm_sym_eig stops whatever the matrix holds */
+
+/* bytes of workspace pfm_sym_eig needs: nothing is kept there, the figure is the least a caller can allocate (0: the arguments
+   are invalid or outside the limits) */
+size_t pfm_sym_eig_workspace_bytes(int64_t batch, int64_t d);
+
+/*
+ * Eigenvalues and eigenvectors of `batch` real symmetric matrices A [batch, d, d], 1 <= d <= PFM_FRECHET_MAX_D, batch <= 65535.
+ * Only the lower triangle and the diagonal of each matrix are read (as np.linalg.eigh does); the matrices need not be positive
+ * semi-definite.  w [batch, d]: the eigenvalues, ascending.  V [batch, d, d] (may be NULL): the eigenvectors, V[b, :, i] belongs to
+ * w[b, i]; their sign is unspecified.  sweeps [batch] (int32, may be NULL): the sweeps that rotated something.
+ * Method: cyclic Jacobi in a parallel (round-robin) order, one workgroup per matrix, A and V in LDS at a row pitch of d | 1 doubles.
+ * With m = d rounded up to even a sweep is m - 1 rounds of m / 2 disjoint index pairs (for odd d one index has a bye).  The rotation
+ * of the pair p < q is SKIPPED where
+ *   |a_pq| <= 2^-53 sqrt|a_pp| sqrt|a_qq|                      (the relative criterion of Demmel & Veselic 1992)
+ * and else taken from tau = (a_qq - a_pp) / (2 a_pq), t = sgn(tau) / (|tau| + sqrt(1 + tau^2)), c = 1 / sqrt(1 + t^2), s = t c; the
+ * pair's new diagonal is a_pp - t a_pq, a_qq + t a_pq and its a_pq exactly 0.  The loop ends after a sweep in which every rotation
+ * was skipped and after PFM_EIG_MAX_SWEEPS sweeps at the latest, so the call terminates on any input: a diagonal matrix takes 0
+ * sweeps; a NaN compares false with the threshold, so a matrix that holds one in the triangle read (d >= 2) runs PFM_EIG_MAX_SWEEPS
+ * sweeps and gets NaN for every eigenvalue and every element of V, and touches no other matrix.  Eigenvalues are ranked with NaN
+ * last and ties by index.  No float atomics; a matrix's outputs are the same bits alone, in any batch, in any call.  On success every
+ * element of every output given is written.
+ * PFM_EINVAL for a NULL A or w, batch outside 1 .. 65535, d < 1; PFM_EUNSUPPORTED for d > PFM_FRECHET_MAX_D; PFM_EWORKSPACE for a
+ * missing or short workspace; on any error nothing is written.
+ */
+int pfm_sym_eig(void *stream, const double *A, int64_t batch, int64_t d, double *w, double *V, int32_t *sweeps,
+                void *workspace, size_t workspace_bytes);
+
+/* bytes of workspace pfm_frechet_grad needs: the moments (mean [2, d] at offset 0, cov [2, d, d] at the next multiple of 256 bytes),
+   the two covariance factors [2, d, d] and the moments' partial sums; nothing of size n d^2 (0: the arguments are invalid or
+   outside the limits) */
+size_t pfm_frechet_grad_workspace_bytes(int64_t n, int64_t d, int64_t n_first);
+
+/*
+ * The Frechet distance of the pooled sample Z [n, d] (the real sample's nr = n_first rows, then the fake sample's nf = n - n_first)
+ * and its row gradients.  Per sample s the mean mu_s and the covariance C_s are pfm_boot_moments' for identity indices, bitwise
+ * (np.cov(rowvar=False), ddof 1, two passes); both samples need at least 2 rows.
+ *   FD = |mu_r - mu_f|^2 + tr C_r + tr C_f - 2 tr (C_r C_f)^(1/2)
+ * The trace term (probaforms_amd/metrics/fd.py, trace_sqrtm): S = C_r^(1/2) from the eigen-decomposition of C_r with the eigenvalues
+ * clipped at 0, M = sym(S C_f S) = V diag(lambda) V^T, tr (C_r C_f)^(1/2) = sum_i sqrt(max(lambda_i, 0)), summed ascending.  The
+ * value always comes from this real-side route.  Both decompositions are pfm_sym_eig's device code.
+ * The gradient: tr f(M) is a spectral function, d tr f(M) = tr(f'(M) dM): no eigenvector derivative appears and repeated
+ * eigenvalues are no special case.  With M^(-1/2)_cut = V diag(c_i) V^T, c_i = lambda_i^(-1/2) where lambda_i > rcond lambda_max
+ * and EXACTLY 0 otherwise (a cut eigenvalue adds the subgradient 0; lambda_max <= 0: nothing is kept),
+ *   G_f = dFD / dC_f = I - S M^(-1/2)_cut S
+ *   G_r = dFD / dC_r = I - T (sym(T C_r T))^(-1/2)_cut T,  T = C_f^(1/2)         (the same route with the samples swapped)
+ *   grad[a, :] = (2 / n_s) (mu_s - mu_o) + (2 / (n_s - 1)) G_s (z_a - mu_s)      for row a of sample s, o the other sample;
+ * the features are summed in ascending order.  An eigenvalue of rounding noise just above the cut gives gradient elements of order
+ * 1 / sqrt(rcond lambda_max): with n <= d or collinear features pass a larger rcond and look at rank.
+ * sides: bit 0 asks for the real rows' gradient, bit 1 for the fake rows'; rows of a sample not asked for are written as 0.  The
+ * swapped route runs only where bit 0 is set and grad is given.  grad [n, d] may be NULL: then only the value is formed.
+ * parts [5] (may be NULL) = { FD, |mu_r - mu_f|^2, tr C_r, tr C_f, tr (C_r C_f)^(1/2) }; eig [d] (may be NULL): lambda of the
+ * real-side M, ascending; rank [2] (int32, may be NULL): the eigenvalues kept by the cut in the real-side route and in the swapped
+ * route, the latter -1 where that route was not run.  On return the workspace holds the moments where
+ * pfm_frechet_grad_workspace_bytes says.
+ * Nothing is checked for NaN or infinity: a NaN anywhere in Z makes the value and every gradient element asked for NaN.  No float
+ * atomics; the order of every sum depends on (n, n_first, d) only, so the outputs are bitwise the same in any call.  On success
+ * every element of every output given is written.
+ * PFM_EINVAL for n_first < 2, n - n_first < 2, d < 1, n >= 2^31, an rcond outside [0, 1) or NaN, sides outside 0 .. 3, sides == 0 with
+ * grad given, a NULL Z or value; PFM_EUNSUPPORTED for d > PFM_FRECHET_MAX_D; PFM_EWORKSPACE for a missing or short workspace; on any
+ * error nothing is written.
+ */
+int pfm_frechet_grad(void *stream, const double *Z, int64_t n, int64_t d, int64_t n_first, double rcond, int sides,
+                     double *value, double *grad, double *parts, double *eig, int32_t *rank, void *workspace,
+                     size_t workspace_bytes);
 
 #ifdef __cplusplus
 }

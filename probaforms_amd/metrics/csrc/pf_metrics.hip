@@ -24,12 +24,14 @@
 //   k_mean_partial / k_mean_final   column sums per part, then the parts in order / n
 //   k_cov_partial / k_cov_final     centred products over row tiles staged in LDS, then the parts in
 //                                   order * 1 / (n - 1)  (np.cov multiplies by the reciprocal)
+// A null index vector means "row r is row r" (pf_moments.h: the samples as given, for pf_frechet.hip).
 #include <hip/hip_runtime.h>
 
 #include <math.h>
 #include <stdint.h>
 
 #include "pf_metrics.h"
+#include "pf_moments.h"
 #include "pf_pairtile.h"
 
 namespace {
@@ -286,16 +288,17 @@ __global__ void k_mmd_final(const MmdState *st, const double *partials, int64_t 
 
 struct Job {
     const double *X;
-    const int32_t *idx;
+    const int32_t *idx;              // NULL: the rows as given
     int64_t n;
+    __device__ int64_t src(int64_t r) const { return idx ? (int64_t)idx[r] : r; }
 };
 
 __device__ inline Job job_of(const double *Xr, int64_t nr, const double *Xf, int64_t nf, const int32_t *idx_r,
                              const int32_t *idx_f, int64_t j) {
     const int64_t rep = j >> 1;
     Job b;
-    if ((j & 1) == 0) { b.X = Xr; b.idx = idx_r + rep * nr; b.n = nr; }
-    else { b.X = Xf; b.idx = idx_f + rep * nf; b.n = nf; }
+    if ((j & 1) == 0) { b.X = Xr; b.idx = idx_r ? idx_r + rep * nr : nullptr; b.n = nr; }
+    else { b.X = Xf; b.idx = idx_f ? idx_f + rep * nf : nullptr; b.n = nf; }
     return b;
 }
 
@@ -320,7 +323,7 @@ __global__ void __launch_bounds__(NT) k_mean_partial(const double *Xr, int64_t n
         const int kk = tid % F, lane = tid / F;
         double acc = 0.0;
         if (lane < lanes && kk < fk)
-            for (int64_t r = r0 + lane; r < r1; r += lanes) acc += b.X[(int64_t)b.idx[r] * d + k0 + kk];
+            for (int64_t r = r0 + lane; r < r1; r += lanes) acc += b.X[b.src(r) * d + k0 + kk];
         red[tid] = acc;
         __syncthreads();
         if (tid < fk) {
@@ -378,7 +381,7 @@ __global__ void __launch_bounds__(NT) k_cov_partial(const double *Xr, int64_t nr
             __syncthreads();
             for (int64_t e = tid; e < rc * d; e += NT) {
                 const int64_t rr = e / d, kk = e - rr * d;
-                rows[e] = b.X[(int64_t)b.idx[c0 + rr] * d + kk] - mu[kk];
+                rows[e] = b.X[b.src(c0 + rr) * d + kk] - mu[kk];
             }
             __syncthreads();
             if (active)
@@ -479,10 +482,32 @@ static bool mom_args_ok(int64_t nr, int64_t nf, int64_t d, int64_t reps) {
     return nr >= 1 && nf >= 1 && d >= 1 && reps >= 1 && 2 * reps <= 65535;
 }
 
-extern "C" size_t pfm_moments_workspace_bytes(int64_t nr, int64_t nf, int64_t d, int64_t reps) {
-    if (!mom_args_ok(nr, nf, d, reps) || d > PFM_MOMENTS_MAX_D) return 0;
+size_t pf_moments_partial_bytes(int64_t nr, int64_t nf, int64_t d, int64_t reps) {
     const int64_t pmax = parts_of(nr > nf ? nr : nf), jobs = 2 * reps;
     return align256(sizeof(double) * jobs * pmax * d) + align256(sizeof(double) * jobs * pmax * (d * (d + 1) / 2));
+}
+
+hipError_t pf_moments_enqueue(hipStream_t st, const double *Xr, int64_t nr, const double *Xf, int64_t nf, int64_t d,
+                              const int32_t *idx_r, const int32_t *idx_f, int64_t reps, double *mean, double *cov,
+                              void *partials) {
+    const int64_t pmax = parts_of(nr > nf ? nr : nf), jobs = 2 * reps;
+    double *mpart = (double *)partials;
+    double *cpart = (double *)((char *)partials + align256(sizeof(double) * jobs * pmax * d));
+    const dim3 grid((unsigned)pmax, (unsigned)jobs);
+    hipError_t e;
+    hipLaunchKernelGGL(k_mean_partial, grid, dim3(NT), 0, st, Xr, nr, Xf, nf, d, idx_r, idx_f, mpart, pmax);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_mean_final, dim3((unsigned)jobs), dim3(NT), 0, st, mpart, pmax, nr, nf, d, mean);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_cov_partial, grid, dim3(NT), 0, st, Xr, nr, Xf, nf, d, idx_r, idx_f, mean, cpart, pmax);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(k_cov_final, dim3((unsigned)jobs), dim3(NT), 0, st, cpart, pmax, nr, nf, d, cov);
+    return hipGetLastError();
+}
+
+extern "C" size_t pfm_moments_workspace_bytes(int64_t nr, int64_t nf, int64_t d, int64_t reps) {
+    if (!mom_args_ok(nr, nf, d, reps) || d > PFM_MOMENTS_MAX_D) return 0;
+    return pf_moments_partial_bytes(nr, nf, d, reps);
 }
 
 extern "C" int pfm_boot_moments(void *stream, const double *Xr, int64_t nr, const double *Xf, int64_t nf, int64_t d,
@@ -492,18 +517,6 @@ extern "C" int pfm_boot_moments(void *stream, const double *Xr, int64_t nr, cons
     if (d > PFM_MOMENTS_MAX_D) return PFM_EUNSUPPORTED;
     const size_t need = pfm_moments_workspace_bytes(nr, nf, d, reps);
     if (!workspace || workspace_bytes < need) return PFM_EWORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t pmax = parts_of(nr > nf ? nr : nf), jobs = 2 * reps;
-    double *mpart = (double *)workspace;
-    double *cpart = (double *)((char *)workspace + align256(sizeof(double) * jobs * pmax * d));
-    const dim3 grid((unsigned)pmax, (unsigned)jobs);
-    hipLaunchKernelGGL(k_mean_partial, grid, dim3(NT), 0, st, Xr, nr, Xf, nf, d, idx_r, idx_f, mpart, pmax);
-    PFM_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_mean_final, dim3((unsigned)jobs), dim3(NT), 0, st, mpart, pmax, nr, nf, d, mean);
-    PFM_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_cov_partial, grid, dim3(NT), 0, st, Xr, nr, Xf, nf, d, idx_r, idx_f, mean, cpart, pmax);
-    PFM_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_cov_final, dim3((unsigned)jobs), dim3(NT), 0, st, cpart, pmax, nr, nf, d, cov);
-    PFM_TRY(hipGetLastError());
+    PFM_TRY(pf_moments_enqueue((hipStream_t)stream, Xr, nr, Xf, nf, d, idx_r, idx_f, reps, mean, cov, workspace));
     return PFM_OK;
 }

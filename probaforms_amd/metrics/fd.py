@@ -1,5 +1,9 @@
 """frechet_distance: probaforms/metrics/fd.py with the bootstrap moments on the GPU (csrc/pf_metrics.hip,
-pfm_boot_moments) and the trace of the matrix square root on the host."""
+pfm_boot_moments) and the trace of the matrix square root on the host.
+
+frechet_distance_full_sample: the distance of the samples as given, wholly on the device (csrc/pf_frechet.hip,
+pfm_frechet_grad: the same moments, then the trace of the matrix square root from two symmetric eigen-decompositions by Jacobi
+rotations in LDS), for at most 64 features; losses.frechet_loss is the same call with a backward()."""
 import numpy as np
 import torch
 
@@ -42,6 +46,32 @@ def frechet_distance(X_real, X_fake, n_iters=100, standardize=False):
     '''
     frd = replicates(X_real, X_fake, n_iters, standardize)
     return frd.mean(axis=0), frd.std(axis=0)
+
+
+def frechet_distance_full_sample(X_real, X_fake, standardize=False):
+    '''
+    The Frechet Distance between real and fake samples as given: no resampling, nothing is drawn from any generator.
+    FD = ||mu_r - mu_f||^2 + tr S_r + tr S_f - 2 tr sqrtm(S_r S_f), as frechet_distance forms it per replicate, computed wholly on
+    the device (pfm_frechet_grad without a gradient).
+
+    Parameters:
+    -----------
+    X_real, X_fake, standardize: as frechet_distance; at least 2 rows each and at most 64 features.
+
+    Return:
+    -------
+    numpy float64.
+
+    Raises ValueError for more than 64 features (there is no fallback) and fewer than 2 rows in a sample.
+    '''
+    from . import _m1d, losses                 # (losses imports this package's host helpers; the call is the loss's)
+    _m1d.check_bool(standardize, "standardize")
+    losses._frechet_shapes(X_real, X_fake)
+    Xr, Xf = _boot.prepare(X_real, X_fake, ("X_real", "X_fake"), 1, standardize)
+    with torch.cuda.device(Xr.device):
+        Z = torch.cat([Xr, Xf], dim=0).contiguous()
+        value = losses._frechet_call(0.0, 0, Z, Xr.shape[0], False)[0]
+        return np.float64(value.item())
 
 
 def replicates(X_real, X_fake, n_iters=100, standardize=False):

@@ -51,6 +51,12 @@ crps_loss(method="sorted") and pinball_loss are the sort-based conditional membe
 and pfm_pinball_grad): every (row, feature) series of draws is sorted by (value, draw) in LDS and scored in one pass, O(K log^2 K)
 per series where the pair walk costs K^2 / 2, for up to 8192 draws.  Once the series is sorted the derivative of the CRPS by a draw is
 a ratio of integers taken from the draw's rank, and the derivative of an empirical quantile touches two order statistics.
+
+frechet_loss is the moment-matching member (kernels: csrc/pf_frechet.hip, pfm_frechet_grad): the Frechet distance of fd.py between the
+two samples' Gaussians, O(n d^2) where energy_loss and mmd_loss walk n^2 pairs, for at most 64 features.  The trace of the matrix
+square root is a spectral function of M = sym(S C_f S), S = C_r^(1/2): its derivative is tr(f'(M) dM), so the backward needs two
+symmetric eigen-decompositions per route (Jacobi, one workgroup, in LDS) and NO eigenvector derivative, whose 1 / (lambda_i - lambda_j)
+terms blow up for close eigenvalues.  With device tensors forward and backward only enqueue work.
 """
 import math
 
@@ -70,7 +76,7 @@ class PooledLossFunction(torch.autograd.Function):
     sinkhorn_loss (pfm_sinkhorn_grad) and sliced_wasserstein_loss / wasserstein_1d_loss (pfm_slice_grad).
 
     call(Z, nr, want_rows) runs the loss's entry point once and returns (value 0-d, rows = dL/dZ [N, d] or None, further 0-d
-    outputs ...): _pair_call, _sinkhorn_call or _slice_call with the loss's constants bound.
+    outputs ...): _pair_call, _sinkhorn_call, _slice_call or _frechet_call with the loss's constants bound.
     forward : the call; rows is kept if an input requires a gradient; -> (value, further outputs ...), the further ones (the
               Sinkhorn drift) marked non-differentiable
     backward: dL/dZ times the incoming scalar, split into the real and the fake rows"""
@@ -252,6 +258,88 @@ class PinballFunction(torch.autograd.Function):
         with torch.cuda.device(side.device):
             _lib.pinball_grad(idx, side, gP.contiguous(), ctx.levels, ctx.K, gx, gy, ws)
         return None, gx, gy
+
+
+def _frechet_call(rcond, sides, Z, nr, want_rows, outputs=None):
+    """pfm_frechet_grad once, as _pair_call: -> (value 0-d, rows [N, d] or None, rank 0-d int32).  sides: bit 0 the real rows'
+    gradient, bit 1 the fake rows' (only what is asked for is formed: with a constant real sample one route runs).  outputs: None or
+    a dict that receives parts [5], eig [d], rank [2] and the workspace"""
+    N, d = Z.shape
+    value, rows, ws = _outputs(Z, want_rows, _lib.frechet_grad_workspace_bytes(N, d, nr))
+    rank = torch.empty(2, dtype=torch.int32, device=Z.device)
+    parts = eig = None
+    if outputs is not None:
+        parts, eig = torch.empty(5, dtype=torch.float64, device=Z.device), torch.empty(d, dtype=torch.float64, device=Z.device)
+        outputs.update(parts=parts, eig=eig, rank=rank, workspace=ws)
+    _lib.frechet_grad(Z, nr, rcond, sides if want_rows else 0, value, rows, parts, eig, rank, ws)
+    return value, rows, rank[0]
+
+
+def _frechet_shapes(X_real, X_fake):
+    """(nr, nf, d) after the shape and dtype checks and the limits of pfm_frechet_grad, before anything touches a device"""
+    d = _features(X_real, X_fake)
+    nr, nf = _boot._check_2d(X_real, NAMES[0])[1][0], _boot._check_2d(X_fake, NAMES[1])[1][0]
+    if d > _lib.FRECHET_MAX_D:
+        raise ValueError("at most %d features, got %d (there is no fallback)" % (_lib.FRECHET_MAX_D, d))
+    if nr < 2 or nf < 2:
+        raise ValueError("both samples need at least 2 rows (the covariance divides by n - 1), got %d and %d" % (nr, nf))
+    return nr, nf, d
+
+
+def _rcond(rcond, d):
+    """None -> d 2^-52 (numpy's matrix_rank / Hermitian pinv: max(M, N) eps); else a float in [0, 1)"""
+    if rcond is None:
+        return d * 2.0 ** -52
+    number = isinstance(rcond, (int, float, np.integer, np.floating)) and not isinstance(rcond, (bool, np.bool_))
+    if not number or not 0.0 <= float(rcond) < 1.0:
+        raise ValueError("rcond must be None or a number in [0, 1), got %r" % (rcond,))
+    return float(rcond)
+
+
+def frechet_loss(X_real, X_fake, standardize=False, rcond=None, return_rank=False):
+    '''
+    The Frechet distance between real and fake samples as a differentiable loss: the value of frechet_distance_full_sample,
+    FD = |mu_r - mu_f|^2 + tr C_r + tr C_f - 2 tr (C_r C_f)^(1/2) with the np.cov covariances (ddof 1). Moment matching is the
+    cheapest two-sample training signal: O(n d^2), where energy_loss and mmd_loss walk n^2 pairs.
+
+    The trace term is sum_i sqrt(max(lambda_i, 0)) over the eigenvalues of M = sym(S C_f S), S = C_r^(1/2) (fd.trace_sqrtm). It is a
+    spectral function of M, so its derivative is tr(f'(M) dM): with M^(-1/2)_cut = V diag(c_i) V^T, c_i = lambda_i^(-1/2) where
+    lambda_i > rcond * lambda_max and exactly 0 otherwise,
+      dFD/dC_f = I - S M^(-1/2)_cut S,   dFD/dC_r the same with the samples swapped,
+      dFD/dz_a = (2 / n_s) (mu_s - mu_o) + (2 / (n_s - 1)) dFD/dC_s (z_a - mu_s)      for row a of sample s, o the other sample.
+    No eigenvector derivative appears: repeated or close eigenvalues are no special case. A cut eigenvalue adds the subgradient 0.
+
+    **An eigenvalue of rounding noise just above the cut gives gradient elements of order 1 / sqrt(rcond * lambda_max).** With
+    n <= d or collinear features the covariance is singular and its zero eigenvalues come out as +-1e-16 lambda_max: pass a larger
+    rcond (1e-10, say) and look at rank (return_rank=True).
+
+    Parameters:
+    -----------
+    X_real, X_fake, standardize: as energy_loss; at least 2 rows each and at most 64 features.
+    rcond: None or float in [0, 1)
+        The relative cut of the eigenvalues in the gradient. Default = None: n_features * 2^-52, numpy's convention for
+        matrix_rank and the Hermitian pinv. It is a constant, and it does not enter the value.
+    return_rank: boolean
+        If True, (loss, rank) is returned, rank a 0-d int32 tensor on the device without a grad_fn: the eigenvalues of M the cut
+        kept (n_features for non-singular data; reading it waits for the device, the call does not). Default = False.
+
+    Return:
+    -------
+    0-d float64 tensor on the device, as energy_loss; only the gradients of the inputs that require one are formed (with a
+    constant real sample one of the two routes runs), and with none only the value. The contents are not checked: a NaN anywhere
+    makes the value and every gradient element NaN. With device tensors forward and backward only enqueue work.
+
+    Raises ValueError for more than 64 features (there is no fallback), fewer than 2 rows in a sample, a bad rcond and non-bool flags.
+    '''
+    _m1d.check_bool(standardize, "standardize")
+    _m1d.check_bool(return_rank, "return_rank")
+    d = _frechet_shapes(X_real, X_fake)[2]
+    rc = _rcond(rcond, d)
+    Xr, Xf = _pooled_inputs(X_real, X_fake, standardize)
+    with torch.cuda.device(Xr.device):
+        sides = (1 if Xr.requires_grad else 0) | (2 if Xf.requires_grad else 0)
+        value, rank = PooledLossFunction.apply(lambda Z, nr, want: _frechet_call(rc, sides, Z, nr, want), Xr, Xf)
+    return (value, rank) if return_rank else value
 
 
 def _gammas(bandwidth):
